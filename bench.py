@@ -1,6 +1,13 @@
 """Benchmark: particle-steps/s (B*N*T / s) of DPF.filtering_pos on synthetic disk tracking.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (value, ms_per_step,
+the last pass's RMSE and resampled steps).  --full adds what takes runs of its own after them: the
+live roofline of the dominant launch, the resampler on its own, the RMSE on informative
+encodings, the `forced` and `informative` lines and the CPU baseline ([--no-cpu-baseline]
+[--no-forced] [--no-informative] leave one out).  --dump-outputs DIR writes the last timed pass's
+outputs as DIR/<name>.npy (dump_outputs).
 
 A "step" is one filtering_pos pass over one batch (B, N, T) -- the hot path of
 BASELINE.json, with the frame encoder replaced by precomputed encodings exactly as the
@@ -325,8 +332,8 @@ def trained_like(dpf, state, seed=1000):
 
 def timed_passes(fcfg, dpf, enc, start, vel_in, shard, args, world, dev):
     """W warm-up passes, then K passes timed between barriers + synchronisations (hipGraph
-    replay of the whole pass where the pass has no host synchronisation), then one more
-    Python-launched pass carrying the live kernel events.  -> dict."""
+    replay of the whole pass where the pass has no host synchronisation), then (--full) one
+    more Python-launched pass carrying the live kernel events.  -> dict."""
     from nfdpf.engine import FilterEngine
     eng = FilterEngine(fcfg, dpf)
 
@@ -453,6 +460,12 @@ def timed_passes(fcfg, dpf, enc, start, vel_in, shard, args, world, dev):
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if world > 1:
+        tt = torch.tensor([elapsed], device=dev, dtype=torch.float64)
+        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+        elapsed = float(tt.item())
+    if not args.full:  # a plain run: the headline figure alone, no live kernel timing
+        return dict(res=res, elapsed=elapsed, kernel_ms=None, front_ms=None, eng=eng, graph=graph, spec=spec)
     # live kernel timing: one more pass right after the timed ones, Python-launched (event nodes
     # inside a graph cannot be timed on ROCm 7), identical kernels and inputs; the tiled step's
     # events ride in the timed launch's own dispatch (hipExtLaunchKernel), every step
@@ -461,16 +474,40 @@ def timed_passes(fcfg, dpf, enc, start, vel_in, shard, args, world, dev):
     torch.cuda.synchronize()
     evs = eng.step_events
     eng.step_events = None
-    if world > 1:
-        tt = torch.tensor([elapsed], device=dev, dtype=torch.float64)
-        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-        elapsed = float(tt.item())
     kernel_ms = float(np.mean([e.ms() for e in evs]))
     front = [e.ms(1) for e in evs if e.n == 4]
     front_ms = float(np.mean(front)) if front else None
     for e in evs:
         e.close()
     return dict(res=res, elapsed=elapsed, kernel_ms=kernel_ms, front_ms=front_ms, eng=eng, graph=graph, spec=spec)
+
+
+DUMP_BYTES = 48 << 20   # --dump-outputs: all files together stay below this (the arrays' data)
+
+
+def dump_outputs(res, out_dir):
+    """Write the last timed pass's FilterResult -- what a caller of FilterEngine.run receives:
+    particles, probs, noise, lik, init_logw, index, jac, prior, obs_likelihood, pred (those that
+    are not None) -- as ``out_dir/<name>.npy``, float32 (integer tensors: float64, exact).  The
+    inputs, the model and the device RNG are seeded, so two runs with the same arguments write the
+    same arrays.  An array beyond its share of DUMP_BYTES is written as a fixed sample: its
+    flattened elements at sorted indices drawn from a generator seeded with 0 (the same indices
+    for the same shape in every run)."""
+    os.makedirs(out_dir, exist_ok=True)
+    names = ("particles", "probs", "noise", "lik", "init_logw", "index", "jac", "prior", "obs_likelihood", "pred")
+    arrs = {}
+    for name in names:
+        t = getattr(res, name, None)
+        if torch.is_tensor(t):
+            t = t.detach()
+            arrs[name] = t.double() if not t.is_floating_point() else t.float() if t.dtype != torch.float64 else t
+    share = DUMP_BYTES // max(1, len(arrs))
+    for name, t in arrs.items():
+        keep = share // t.element_size()
+        if t.numel() > keep:
+            idx = np.sort(np.random.default_rng(0).integers(0, t.numel(), size=keep))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy())
 
 
 def dominant(cfg_name, flags, kernel, B, N, T, fcfg, run, force):
@@ -568,13 +605,20 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
     ap.add_argument("--force-resample", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure: the live roofline of the dominant launch, the resampler on "
+                         "its own, the RMSE on informative encodings, the `forced` and `informative` lines and the "
+                         "CPU baseline (each in runs of its own after the timed steps; see --no-*)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed pass returned (FilterResult's tensors, "
+                         "rank 0's rows) as DIR/<name>.npy; see dump_outputs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the line's `cpu_baseline`")
     ap.add_argument("--no-forced", action="store_true",
-                    help="skip the line's `forced` object (the same workload with --force-resample, timed "
-                         "in a second loop; on by default for the configurations whose pass takes < 30 ms)")
+                    help="with --full: skip the line's `forced` object (the same workload with --force-resample, "
+                         "timed in a second loop; there for the configurations whose pass takes < 30 ms)")
     ap.add_argument("--no-informative", action="store_true",
-                    help="skip the line's `informative` object (the same workload on informative frame encodings, "
-                         "where the ESS gate fires on most steps, timed in its own loop; on by default for c1-c3)")
+                    help="with --full: skip the line's `informative` object (the same workload on informative frame "
+                         "encodings, where the ESS gate fires on most steps, timed in its own loop; there for c1-c3)")
     ap.add_argument("--batch", type=int, default=None, help="override B per GPU (exploration only)")
     ap.add_argument("--graph", type=int, default=1,
                     help="1: capture the whole T-step pass (all launches of filtering_pos) in a hipGraph and "
@@ -625,8 +669,12 @@ def main():
         fcfg.speculate_gate = bool(args.speculate)
     run = timed_passes(fcfg, dpf, enc, start, vel_in, shard, args, world, dev)
     res, elapsed, eng, graph, spec = run["res"], run["elapsed"], run["eng"], run["graph"], run["spec"]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(res, args.dump_outputs)
+    if not args.full:  # a plain run stops at the headline figure: none of the lines timed beside it
+        args.no_forced = args.no_informative = args.no_cpu_baseline = True
     roof, ot_iter_ms, ot_iter_upper = dominant(args.config, flags, args.kernel, B, N, T, fcfg, run,
-                                               args.force_resample)
+                                               args.force_resample) if args.full else (None, None, False)
     front_ms = run["front_ms"]
     # filtering RMSE of the last pass (losses.py:18-31, eval branch) over the whole job
     se = ((res.pred - state[:, :, :2]) ** 2).sum().double()
@@ -640,7 +688,7 @@ def main():
     # carry no information, so their RMSE is not a filtering-quality number.  One untimed pass
     # on its own engine (the timed engine's speculation state is left alone).
     rmse_inf, enc_inf = None, None
-    if not args.enc_from_state:
+    if args.full and not args.enc_from_state:
         with torch.no_grad():
             enc_inf = dpf.particle_encoder(state[:, :, :2].float()).contiguous()
         res_inf = FilterEngine(fcfg, dpf).run(enc_inf, start, vel_in, shard=shard)
@@ -657,7 +705,10 @@ def main():
         resampled = int((res.index != ident[:, None, :]).flatten(2).any(-1).any(0).sum())
 
     # the resampler on its own (timed with --force-resample as well as gated)
-    if flags["resampler_type"] == "soft":
+    resample = None
+    if not args.full:
+        pass
+    elif flags["resampler_type"] == "soft":
         rs_ms = soft_resample_ms(res, T)
         rs_gbs = B_SOFT * B * N / (rs_ms * 1e-3) / 1e9
         resample = {"kernel": "soft_resample_kernel (standalone nfdpf_soft_resample on slot T/2)",
@@ -678,7 +729,7 @@ def main():
                     "ot_iter_ms_is_upper_bound": ot_iter_upper, "calls_in_last_pass": eng.last_ot_calls}
         if ot_iter_upper:  # the 10 / 20-iteration difference was swamped: no rate from an upper bound
             resample["achieved_TFLOPs"] = resample["frac"] = None
-    if front_ms is not None:
+    if front_ms is not None and resample is not None:
         resample["front_launch_ms"] = front_ms  # the step's gate + resampling + motion launch, live
 
     # the same workload with the resampler every step (--force-resample), timed in its own loop
@@ -753,11 +804,10 @@ def main():
                        "global_batch": B * world, "num_particles": N, "seq_len": T,
                        "parallelism": f"batch-sharded x{world}"},
             "rmse": rmse,
-            "rmse_informative_encodings": rmse_inf,
             "resampled_steps": resampled,
-            "roofline": roof,
-            "resample": resample,
         }
+        if args.full:
+            out.update({"rmse_informative_encodings": rmse_inf, "roofline": roof, "resample": resample})
         if forced is not None:
             out["forced"] = forced
         if informative is not None:

@@ -3,7 +3,7 @@
 # -> gpurun_out/pmc_<tag>_<pass>/ ; summarise with scripts/pmc_summary.py
 export TMPDIR=/tmp
 TAG=${TAG:-r01}
-ARGS=${BENCH_ARGS:---steps 1 --warmup 1 --no-cpu-baseline}
+ARGS="--full ${BENCH_ARGS:---steps 1 --warmup 1 --no-cpu-baseline}"  # (--full: the forced / informative lines' kernels too)
 mkdir -p gpurun_out
 run() {
   timeout -k 10 ${PMC_TIMEOUT:-240} rocprofv3 --pmc $2 --output-format csv -d gpurun_out/pmc_${TAG}_$1 -o run -- \

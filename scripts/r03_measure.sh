@@ -7,6 +7,9 @@
 #      (gpurun_out/pmc_<tag>.csv); bench.py reads both back from profiles/ once committed there
 export TMPDIR=/tmp
 mkdir -p gpurun_out
+# the bench lines and their profiles hold more than the headline figure: bench.py --full
+BENCH_ARGS="--full ${BENCH_ARGS}"
+PROF_ARGS="--full ${PROF_ARGS}"
 fatal() { case "$1" in 0|1|2|5) return 1;; *) return 0;; esac; }
 case "$PART" in
 1)

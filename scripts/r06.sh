@@ -11,6 +11,9 @@
 export TMPDIR=/tmp
 O=gpurun_out/r06
 mkdir -p $O
+# the bench lines and their profiles hold more than the headline figure: bench.py --full
+BENCH_ARGS="--full ${BENCH_ARGS:---no-cpu-baseline}"
+PROF_ARGS="--full ${PROF_ARGS}"
 n=0
 spec_parse() {  # -> cfg, extra, tag, envs
   local s=$1; cfg=${s%%:*}; extra=""; tag=$cfg; envs=""
