@@ -29,7 +29,8 @@
 //      the tile's merged partial -> ess_out[t - 1]] -> normalise slot t - 1 of the group from
 //      the other wave's hand-over nb (finish_prev's arithmetic: hist_p, hist_lik shifted, the
 //      fin partials) -> log p_{t-1};
-//   4. u_t, the group's partials {max u, sum e, sum e^2, max lik} -> C(t) granules.
+//   4. u_t, the group's partials {max u, sum e, sum e^2, max lik} -> C(t) granules (shifted
+//      measurements: u relative to the group's max lik).
 // The waves of k = T mod K normalise the last slot after their loop.
 //
 // Every wait is bounded (pass_spin: 200 ms, the workspace's abort word), as in filter_pass.hpp.
@@ -95,39 +96,46 @@ __device__ __forceinline__ void pass_cm_poll_c(const nfdpf_filter_desc &d, const
   }
   if (got) {
     const int k = lane < tiles ? lane : 0;
-    float m = -INFINITY, lm = -INFINITY;
+    // SHIFT: a group's max u and sums are relative to its own max raw likelihood (word 5; the
+    // kernel's step 4), so nothing here is rounded at the raw likelihood's magnitude: the groups
+    // merge relative to the tile's max raw likelihood, the tiles relative to the row's
+    float lm = -INFINITY;
+#pragma unroll
+    for (int v = 0; v < 4; ++v) lm = fmaxf(lm, __uint_as_float(L.rowc[(k * 4 + v) * kGC + 5]));
+    float a[4], m = -INFINITY;
 #pragma unroll
     for (int v = 0; v < 4; ++v) {
-      m = fmaxf(m, __uint_as_float(L.rowc[(k * 4 + v) * kGC]));
-      lm = fmaxf(lm, __uint_as_float(L.rowc[(k * 4 + v) * kGC + 5]));
+      const float mv = __uint_as_float(L.rowc[(k * 4 + v) * kGC]);
+      a[v] = SHIFT && mv > -INFINITY ? mv + (__uint_as_float(L.rowc[(k * 4 + v) * kGC + 5]) - lm) : mv;
+      m = fmaxf(m, a[v]);
     }
     double sum = 0.0, sq = 0.0;
 #pragma unroll
     for (int v = 0; v < 4; ++v) {
       const int q = (k * 4 + v) * kGC;
-      const float mv = __uint_as_float(L.rowc[q]);
-      if (mv > -INFINITY) {
-        const double f = (double)expf(mv - m);
+      if (a[v] > -INFINITY) {
+        const double f = (double)expf(a[v] - m);
         sum += lds_double(L.rowc, q + 1) * f;
         sq += lds_double(L.rowc, q + 3) * f * f;
       }
     }
     if (lane == tile) {
       double *sm = reinterpret_cast<double *>(d.ess_out) + (((int64_t)s * d.B + b) * tiles + tile) * kSm;
-      sm[0] = m;
+      sm[0] = SHIFT ? (double)m + (double)lm : (double)m;  // max u as the partials carry it (fp64: exact)
       sm[1] = sum;
       sm[2] = sq;
       sm[3] = lm;
     }
-    // row_norm (filter_tiled.hip) over the tiles in order, shifted by the row max raw likelihood
-    float M = -INFINITY, Lmax = -INFINITY;
-    for (int kk = 0; kk < tiles; ++kk) {
-      M = fmaxf(M, (float)(double)readlane_f(m, kk));
-      Lmax = fmaxf(Lmax, readlane_f(lm, kk));
-    }
+    // row_norm (filter_tiled.hip) over the tiles in order, shifted by the row max raw likelihood:
+    // mr = the tile's max of u - Lmax, the reference's shifted log-weight (model/models.py:276)
+    float Lmax = -INFINITY;
+    for (int kk = 0; kk < tiles; ++kk) Lmax = fmaxf(Lmax, readlane_f(lm, kk));
+    const float mr = SHIFT ? (float)(((double)m + (double)lm) - (double)Lmax) : m;  // row_norm's, from sm[0]
+    float M = -INFINITY;
+    for (int kk = 0; kk < tiles; ++kk) M = fmaxf(M, readlane_f(mr, kk));
     double Sd = 0.0;
-    for (int kk = 0; kk < tiles; ++kk) Sd += readlane_d(sum, kk) * (double)expf(readlane_f(m, kk) - M);
-    if (lane == 0) L.rn[s & 1] = SHIFT ? RowNorm{M - Lmax, (float)Sd, Lmax} : RowNorm{M, (float)Sd, 0.f};
+    for (int kk = 0; kk < tiles; ++kk) Sd += readlane_d(sum, kk) * (double)expf(readlane_f(mr, kk) - M);
+    if (lane == 0) L.rn[s & 1] = SHIFT ? RowNorm{M, (float)Sd, Lmax} : RowNorm{M, (float)Sd, 0.f};
   }
   set_flag(&L.fR, s + 1);
 }
@@ -264,16 +272,19 @@ __global__ __launch_bounds__(4 * K * 64, 1) void tiled_pass_cm_kernel(const nfdp
       lr = pass_cm_norm<SHIFT>(d, ws, L, b, tile, g, t - 1, slot, i, valid);
     }
     // 4. the log-weight (DPFs.py:187) and exchange C(t): this group's softmax partials
+    // (SHIFT: u relative to the wave's max raw likelihood, so that a raw likelihood of ~1e3
+    // does not round the log-weights at its own magnitude; pass_cm_poll_c merges accordingly)
+    const float lmw = wave_max_dpp(raw);
     float u = -INFINITY;
     if (valid) {
-      u = ((lr + raw) + de) - de;
+      u = ((lr + (SHIFT ? raw - lmw : raw)) + de) - de;
       L.nb[par][0][slot] = lr;
       L.nb[par][1][slot] = raw;
       L.nb[par][2][slot] = de;
       L.nb[par][3][slot] = x0;
       L.nb[par][4][slot] = x1;
     }
-    const float mw = wave_max_dpp(u), lmw = wave_max_dpp(raw);
+    const float mw = wave_max_dpp(u);
     const float ev = valid ? expf(u - mw) : 0.f;
     double r[2] = {(double)ev, (double)ev * ev};
     wave_sum_dpp_n(r);

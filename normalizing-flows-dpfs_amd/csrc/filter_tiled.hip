@@ -184,29 +184,48 @@ struct RowNorm {
 template <int KT, class SM>
 __device__ __forceinline__ RowNorm row_norm_t(const SM &sm, int tiles, bool shifted) {
   float M = -INFINITY, Lmax = -INFINITY;
+  if (shifted) {  // (see row_norm: max u - Lmax formed in fp64)
+#pragma unroll
+    for (int k = 0; k < KT; ++k)
+      if (k < tiles) Lmax = fmaxf(Lmax, (float)sm(kSm * k + 3));
+#pragma unroll
+    for (int k = 0; k < KT; ++k)
+      if (k < tiles) M = fmaxf(M, (float)(sm(kSm * k) - (double)Lmax));
+    double Sd = 0.0;
+#pragma unroll
+    for (int k = 0; k < KT; ++k)
+      if (k < tiles) Sd += sm(kSm * k + 1) * (double)expf((float)(sm(kSm * k) - (double)Lmax) - M);
+    return RowNorm{M, (float)Sd, Lmax};
+  }
 #pragma unroll
   for (int k = 0; k < KT; ++k) {
     if (!(k < tiles)) continue;
     M = fmaxf(M, (float)sm(kSm * k));
-    if (shifted) Lmax = fmaxf(Lmax, (float)sm(kSm * k + 3));
   }
   double Sd = 0.0;
 #pragma unroll
   for (int k = 0; k < KT; ++k)
     if (k < tiles) Sd += sm(kSm * k + 1) * (double)expf((float)sm(kSm * k) - M);
-  return RowNorm{shifted ? M - Lmax : M, (float)Sd, Lmax};
+  return RowNorm{M, (float)Sd, Lmax};
 }
 __device__ __forceinline__ RowNorm row_norm(const double *sm_, int tiles, bool shifted) {
   gdouble *sm = (gdouble *)sm_;
   float M = -INFINITY, Lmax = -INFINITY;
-  for (int k = 0; k < tiles; ++k) {
-    M = fmaxf(M, (float)sm[kSm * k]);
-    if (shifted) Lmax = fmaxf(Lmax, (float)sm[kSm * k + 3]);
+  if (shifted) {
+    // u = logw + Lmax for the shifted models: normalise with the same shift.  The partials
+    // carry max u in fp64 (a raw likelihood of ~1e3 would round a float max u at its own
+    // magnitude, 1e-4): max u - Lmax, the reference's shifted log-weight, is formed in fp64
+    for (int k = 0; k < tiles; ++k) Lmax = fmaxf(Lmax, (float)sm[kSm * k + 3]);
+    for (int k = 0; k < tiles; ++k) M = fmaxf(M, (float)(sm[kSm * k] - (double)Lmax));
+    double Sd = 0.0;
+    for (int k = 0; k < tiles; ++k)
+      Sd += sm[kSm * k + 1] * (double)expf((float)(sm[kSm * k] - (double)Lmax) - M);
+    return RowNorm{M, (float)Sd, Lmax};
   }
+  for (int k = 0; k < tiles; ++k) M = fmaxf(M, (float)sm[kSm * k]);
   double Sd = 0.0;
   for (int k = 0; k < tiles; ++k) Sd += sm[kSm * k + 1] * (double)expf((float)sm[kSm * k] - M);
-  // u = logw + Lmax for the shifted models: normalise with the same shift
-  return RowNorm{shifted ? M - Lmax : M, (float)Sd, Lmax};
+  return RowNorm{M, (float)Sd, Lmax};
 }
 
 // ESS gate: torch.mean over the batch of the rows' 1/sum p^2 (ATen's cascade order),
@@ -1083,6 +1102,48 @@ __device__ __forceinline__ void store_softmax(float u, bool valid, double *sm, f
   }
 }
 
+// store_softmax for a shifted measurement whose raw likelihood may be large (CRNVP: ~1e3 at
+// trained weights): u is the log-weight with the likelihood taken relative to lmw, the wave's max
+// raw likelihood (so nothing is rounded at the raw likelihood's magnitude); the waves merge
+// relative to the tile's max raw likelihood lm (-> sm[3]) and sm[0] = max u in fp64, m + lm
+// (tiled_pass_cm_kernel's pass_cm_poll_c, the same arithmetic).  shd >= 24 doubles.
+__device__ __forceinline__ void store_softmax_rel(float u, bool valid, float lmw, double *sm, float *shf,
+                                                  double *shd) {
+  const float mw = wave_max_dpp(valid ? u : -INFINITY);
+  const float ev = valid ? expf(u - mw) : 0.f;
+  const double ew = wave_sum_dpp((double)ev);
+  const double qw = wave_sum_dpp((double)ev * ev);
+  const int w = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) {
+    shf[w] = mw;
+    shd[2 * w] = ew;
+    shd[2 * w + 1] = qw;
+    shd[16 + w] = (double)lmw;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const int nw = (blockDim.x + 63) >> 6;
+    float lm = -INFINITY;
+    for (int k = 0; k < nw; ++k) lm = fmaxf(lm, (float)shd[16 + k]);
+    float m = -INFINITY;
+    for (int k = 0; k < nw; ++k) {
+      if (shf[k] > -INFINITY) shf[k] = shf[k] + ((float)shd[16 + k] - lm);
+      m = fmaxf(m, shf[k]);
+    }
+    double sum = 0.0, sq = 0.0;
+    for (int k = 0; k < nw; ++k)
+      if (shf[k] > -INFINITY) {
+        const double f = (double)expf(shf[k] - m);
+        sum += shd[2 * k] * f;
+        sq += shd[2 * k + 1] * f * f;
+      }
+    sm[0] = (double)m + (double)lm;
+    sm[1] = sum;
+    sm[2] = sq;
+    sm[3] = lm;
+  }
+}
+
 // store_softmax (role-0 lanes carry u) plus, with the same barrier, the four deferred-
 // normalisation sums of the role-1 waves (block_sum_roles_store's order) into fin.
 // smd >= 48 doubles.
@@ -1183,9 +1244,9 @@ __global__ __launch_bounds__(kTile) void tiled_prop_kernel(const nfdpf_filter_de
   if (!NFD && d.defer_norm && d.t > 0)  // no K2 in this config
     finish_prev(d, ws, b, tile, i, true, i < d.N ? load_prev_in(row_slot(d, b, d.t - 1), i) : PrevIn{}, L.d);
   TRACE(2, 1)
-  float lk = -INFINITY, u = 0.f;
+  float lk = -INFINITY, u = 0.f, propose = 0.f, prior = 0.f;
   if constexpr (MF) {  // the proposal per lane, then the wave's 64 likelihoods on MFMA
-    float q0x = 0.f, q1x = 0.f, propose = 0.f, prior = 0.f;
+    float q0x = 0.f, q1x = 0.f;
     if (valid) {
       const float jp = stage_propose_inverse<NFC>(d, in, L.cb_cond, q0x, q1x);
       stage_prior<NFD, NFC>(d, S, i, in, L.cb_dyn, q0x, q1x, jp, propose, prior);
@@ -1202,7 +1263,7 @@ __global__ __launch_bounds__(kTile) void tiled_prop_kernel(const nfdpf_filter_de
       u = logw(lr, lk, prior, propose);
     }
   } else if (valid) {
-    float q0x, q1x, propose, prior;
+    float q0x, q1x;
     if constexpr (STAGE) {
       static_assert(!STAGE || MEAS == NFDPF_MEAS_CRNVP, "staged weights: CRNVP only");
       const float jp = stage_propose_inverse<NFC>(d, in, L.cb_cond, q0x, q1x);
@@ -1220,10 +1281,16 @@ __global__ __launch_bounds__(kTile) void tiled_prop_kernel(const nfdpf_filter_de
   TRACE(2, 2)
   if (MEAS == NFDPF_MEAS_EXTERNAL) return;  // phase 1: the external likelihood comes next
   double *sm = reinterpret_cast<double *>(d.ess_out) + ((int64_t)b * tiles + tile) * kSm;
-  const float lm = meas_shifted<MEAS>() ? block_max_dpp(lk, L.f) : 0.f;
-  if (threadIdx.x == 0) sm[3] = lm;
   __shared__ double smd[48];
-  store_softmax(u, valid, sm, L.f + 8, smd);  // L.f[0:8] held block_max
+  if constexpr (MEAS == NFDPF_MEAS_CRNVP) {  // the log-weight relative to the wave's max raw likelihood
+    const float lmw = wave_max_dpp(lk);
+    if (valid) u = logw(lr, lk - lmw, prior, propose);
+    store_softmax_rel(u, valid, lmw, sm, L.f + 8, smd);
+  } else {
+    const float lm = meas_shifted<MEAS>() ? block_max_dpp(lk, L.f) : 0.f;
+    if (threadIdx.x == 0) sm[3] = lm;
+    store_softmax(u, valid, sm, L.f + 8, smd);  // L.f[0:8] held block_max
+  }
   TRACE(2, 3)
 }
 
@@ -1372,7 +1439,7 @@ __global__ __launch_bounds__(2 * kTile) void tiled_prop_cm_kernel(const nfdpf_fi
   TRACE(2, 1)
   const int nh = 2 * d.n_flows;
   lds_vint *flag = (lds_vint *)&cflag[__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) & 3];
-  float lk = -INFINITY, u = 0.f;
+  float lk = -INFINITY, u = 0.f, propose = 0.f, prior = 0.f;
   if (!flows) {
     float e[kE];
     particle_encode<kE>(wptr(d.pe_params), in.xd0, in.xd1, e);
@@ -1384,7 +1451,6 @@ __global__ __launch_bounds__(2 * kTile) void tiled_prop_cm_kernel(const nfdpf_fi
       *flag = h + 1;
     }
   } else {
-    float propose = 0.f, prior = 0.f;
     if (valid) stage_prior<NFD, false>(d, S, i, in, nullptr, in.xd0, in.xd1, 0.f, propose, prior);
     float lo[HALF], up[HALF];
 #pragma unroll
@@ -1437,9 +1503,10 @@ __global__ __launch_bounds__(2 * kTile) void tiled_prop_cm_kernel(const nfdpf_fi
   }
   TRACE(2, 2)
   double *sm = reinterpret_cast<double *>(d.ess_out) + ((int64_t)b * tiles + tile) * kSm;
-  const float lm = block_max_dpp(lk, L.f);  // the cond waves hold -inf
-  if (threadIdx.x == 0) sm[3] = lm;
-  store_softmax(u, valid && flows, sm, smf, smd);
+  // the log-weight relative to the wave's max raw likelihood (tiled_prop_kernel's); the cond waves hold -inf
+  const float lmw = wave_max_dpp(lk);
+  if (valid && flows) u = logw(lr, lk - lmw, prior, propose);
+  store_softmax_rel(u, valid && flows, lmw, sm, smf, smd);
   TRACE(2, 3)
 }
 

@@ -1032,6 +1032,20 @@ class FilterEngine:
         p, self._pending = self._pending, None
         return p
 
+    @staticmethod
+    def pending_pass_state(pending) -> dict:
+        """The ``take_pending()`` state of a one-shard speculative one-launch pass by name,
+        read-only (nothing is verified, consumed or changed; for tests): ``gates`` [T] int32, the
+        gates its epilogue evaluated from every step's partials; ``obs``, the obs-likelihood it
+        reduced (valid whether or not a gate fired); ``parts`` [T, B, tiles, 4] fp64, step t's
+        input softmax partials; ``flags`` (gates fired, hand-off faults, written), host ints.
+        The caller has synchronised the pass's stream."""
+        verify = pending[6]
+        if verify is None or not pending[7] or len(pending) < 11 or pending[10] is None:
+            raise L.NfdpfError("pending_pass_state: not the state of a one-shard speculative one-launch pass")
+        flags = verify[2][:3] if verify[0] is None else verify[0].tolist()[:3]
+        return dict(gates=pending[10], obs=verify[1], parts=pending[0], flags=tuple(int(v) for v in flags))
+
     def finish_pending(self, pending=None, synced: bool = False) -> bool:
         """Verify the speculative pass of the last ``run`` (or the given ``take_pending()``
         state; its buffers, so also after a graph replay of it): gather every step's softmax

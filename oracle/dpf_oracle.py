@@ -578,11 +578,17 @@ class HostRNG:
 
 
 def filter_step(cfg: dict, params: Params, meas: Callable, x, p, vel, enc_t, rng: HostRNG,
-                force_resample=False):
+                force_resample=False, gate: Optional[bool] = None):
     """One iteration of the T loop of DPF.filtering_pos (DPFs.py:160-214).
 
     ``x``/``p`` are the particles / probabilities after the previous step, ``vel`` the
-    velocity used by this step's motion.  Returns a dict of this step's history entries.
+    velocity used by this step's motion.  Returns a dict of this step's history entries,
+    with the reference's ``ess`` expression (:162) as evaluated for this step's gate.
+
+    ``gate`` (TEST-ONLY, not a mode of the reference): a bool replaces the ESS decision --
+    the step resamples iff ``gate`` -- so that a run with every gate held off (no discrete
+    decision anywhere) can be compared at any weight scale.  ``ess`` is evaluated and
+    returned all the same.  None (the default) is the reference's own decision.
     """
     N = cfg["N"]
     B = x.shape[0]
@@ -590,7 +596,7 @@ def filter_step(cfg: dict, params: Params, meas: Callable, x, p, vel, enc_t, rng
     dyn_p, cond_p = sub(params, "nf_dyn"), sub(params, "cond_model")
     idx = (torch.arange(N) + N * torch.arange(B)[:, None].repeat((1, N))).long()
     ess = torch.mean(1 / torch.sum(p ** 2, dim=-1))
-    fired = bool(force_resample or ess < 0.5 * N)
+    fired = bool(force_resample or ess < 0.5 * N) if gate is None else bool(gate)
     if fired:
         if cfg["resampler"] == "soft":
             xr, pr, idx = soft_resample(x, p, cfg["alpha"], rng.offsets(B, N))
@@ -607,7 +613,7 @@ def filter_step(cfg: dict, params: Params, meas: Callable, x, p, vel, enc_t, rng
                                                cfg["pos_noise"], cfg["vel_noise"], dyn_kind=dk)
     lw = lr + lik + prior - prop
     return dict(x=xp, p=normalize_log_probs(lw) + 1e-12, noise=noise, lik=lik, idx=idx, jac=jac,
-                prior=prior, lw_mean=lw.mean(), fired=fired, logw=lw)
+                prior=prior, lw_mean=lw.mean(), fired=fired, logw=lw, ess=ess)
 
 
 def make_measurement(cfg: dict, params: Params) -> Callable:
@@ -629,16 +635,21 @@ def make_measurement(cfg: dict, params: Params) -> Callable:
 
 
 def filtering(cfg: dict, params: Params, enc: torch.Tensor, start_state, vel_input,
-              rng: Optional[HostRNG] = None, force_resample=False, init=None):
+              rng: Optional[HostRNG] = None, force_resample=False, init=None, gates=None):
     """DPF.filtering_pos (DPFs.py:144-216) with precomputed frame encodings ``enc`` (B,T,H).
 
     ``cfg`` keys: N, NF_dyn, NF_cond, measurement, resampler ('soft'|'ot'), alpha, eps, scaling,
     threshold, max_iter, pos_noise, vel_noise, width, n_flows, init_with_true_state, cglow_K.
     History is concatenated step by step as the reference does (:207-214).
     Returns the reference's 9-tuple.
+
+    ``gates`` (TEST-ONLY, see filter_step): a length-T sequence of bools replacing the ESS
+    decisions -- step t resamples iff ``gates[t]``.  None: the reference's own gates.
     """
     rng = rng or HostRNG()
     N, T = cfg["N"], enc.shape[1]
+    if gates is not None and len(gates) != T:
+        raise ValueError(f"gates: {len(gates)} entries for T = {T} steps")
     meas = make_measurement(cfg, params)
     if init is None:
         x, logw0 = particle_init(start_state[:, :2], cfg["width"], N, 2,
@@ -651,7 +662,10 @@ def filtering(cfg: dict, params: Params, enc: torch.Tensor, start_state, vel_inp
     keys = ("x", "p", "noise", "lik", "idx", "jac", "prior")
     hist = {}
     for t in range(T):
-        r = filter_step(cfg, params, meas, x, p, vel, enc[:, t], rng, force_resample)
+        if gates is None:
+            r = filter_step(cfg, params, meas, x, p, vel, enc[:, t], rng, force_resample)
+        else:
+            r = filter_step(cfg, params, meas, x, p, vel, enc[:, t], rng, force_resample, gate=bool(gates[t]))
         vel = vel_input[:, t, :]
         x, p = r["x"], r["p"]
         obs_lik += r["lw_mean"]

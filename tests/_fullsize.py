@@ -35,7 +35,16 @@ CASES = {
     # CGLOW kernel's persistent grid (768 workgroups x 16 particles) takes ~7 tiles per workgroup
     "c5_n10000": (dict(NF_dyn=True, NF_cond=True, measurement="CGLOW", resampler="soft"), 8, 10000, 3, 0.5, 0.05,
                   0.1, True),
+    # c3_full's model with a milder particle encoder (std 0.2): without resampling its ESS / N
+    # decays slowly (4 x 1000 x 7: 0.60, 0.41, 0.34, 0.24, 0.19, 0.13, 0.11), so hundreds of
+    # particles carry weight at every step and the gates are mixed (off, off, on, ...) -- the
+    # scale at which weights and gates are compared hardest.  A weight scale for workload() with
+    # the caller's own B / N / T (tests/test_gpu_cm_trained.py); not a full-size case (FULL_CASES).
+    "c3_mid": (dict(NF_dyn=False, NF_cond=False, measurement="CRNVP", resampler="ot"), 64, 1000, 10, 0.2, 0.05, 0.1,
+               False),
 }
+# the cases run at their own sizes with the host RNG (tests/test_gpu_parity_full.py)
+FULL_CASES = ("c2_full", "c3_full", "c4_n4000", "c5_n10000")
 
 
 def cfg_dict(flags, N):

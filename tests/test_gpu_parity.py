@@ -815,3 +815,36 @@ def test_crnvp_mfma_matches_valu(N, nf_dyn, resampler, force, monkeypatch):
     # largest such factor): twice the likelihood bound, relative
     pa, pb = a.probs[:, 0].cpu(), b.probs[:, 0].cpu()
     assert bool(((pa - pb).abs() <= 2 * tol.amax(-1, keepdim=True) * pb + 1e-9).all())
+    # ... and both against the reference: step 0 of the oracle (float32 and float64) from the same
+    # initial particles (the engine's device draw, seed 7: particle_init's) and the launch's own
+    # noise.  Step 0's weights are uniform, so its gate is off unless forced; forced, the oracle
+    # resamples them as the launch does (OT: its own FP64 Sinkhorn, one call at this size).
+    # Both launches must sit inside the float32 oracle's own error envelope against float64
+    # (_check_envelope, the constants of test_gpu_pass_cm.test_cm_pass_vs_oracle), which says
+    # which side is nearer the truth, not only that the two agree.
+    from nfdpf import ops
+    from test_gpu_pass import _Replay
+    B = wl["B"]
+    start = wl["start"].to(DEV)
+    x0, logw0 = ops.particle_init(start[:, :2], B, N, 128.0, False, 7, 0, DEV)
+    if not nf_dyn and not force:  # the bootstrap proposal: x_0 = (x0 + vel) + eps, the same two adds
+        assert torch.equal(a.particles[:, 0], (x0 + start[:, None, 2:4]) + a.noise[:, 0]), "not the engine's initial draw"
+    c = F.cfg_dict(dict(wl["flags"], NF_dyn=nf_dyn, resampler=resampler), N)
+    w = {k: v.detach().float().cpu() for k, v in models.state_dict().items()}
+    refs = {}
+    for dt in (torch.float32, torch.float64):
+        with O.precision(dt), torch.no_grad():
+            r = O.filtering(c, O.cast_params(w, dt), wl["enc"][:, :1].cpu().to(dt), wl["start"].cpu().to(dt),
+                            wl["vel"][:, :1].cpu().to(dt), rng=_Replay(a.noise[:, :1]), force_resample=force,
+                            init=(x0.cpu().to(dt), logw0.cpu().to(dt)))
+        refs[dt] = (r[3].double().numpy(), r[1].double().numpy())  # lik, probs: [B, 1, N]
+    (l32, p32), (l64, p64) = refs[torch.float32], refs[torch.float64]
+    print(f"\nCRNVP step 0 vs oracle, N={N} nf_dyn={nf_dyn} {resampler} force={force}: float32 oracle max err "
+          f"lik {np.abs(l32 - l64).max():.3e} weights {np.abs(p32 - p64).max():.3e}")
+    ours = {tag: (run.lik[:, :1].cpu().double().numpy(), run.probs[:, :1].cpu().double().numpy())
+            for tag, run in (("mfma", a), ("valu", b))}
+    for tag, (lo, po) in ours.items():  # (every figure before any assertion)
+        print(f"  {tag}: max err lik {np.abs(lo - l64).max():.3e} weights {np.abs(po - p64).max():.3e}")
+    for tag, (lo, po) in ours.items():
+        _check_envelope(lo, l32, l64, 1e-5, 2e-5, f"{tag} likelihood")
+        _check_envelope(po, p32, p64, 1e-5, 1e-9, f"{tag} weights")

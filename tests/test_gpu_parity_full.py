@@ -152,7 +152,7 @@ def _r64(name, w):
 
 
 @pytest.mark.timeout(900)
-@pytest.mark.parametrize("name", list(F.CASES))
+@pytest.mark.parametrize("name", list(F.FULL_CASES))
 def test_fullsize_teacher_forced(name):
     from test_gpu_parity import _check_envelope
     w = _case(name)
@@ -333,7 +333,7 @@ def test_ot_stop_at_c4_share():
 
 
 @pytest.mark.timeout(900)
-@pytest.mark.parametrize("name", list(F.CASES))
+@pytest.mark.parametrize("name", list(F.FULL_CASES))
 def test_fullsize_free_running(name):
     w = _case(name)
     ref = w["ref"]
