@@ -268,20 +268,26 @@ NFDPF_API int nfdpf_nn_measurement_backward(const float *meas_params, const floa
                                             float *g_params, void *workspace, void *stream);
 
 /* Conditional-GLOW measurement (model/models.py:280-303; nf/cglow/CGlowModel.py with the
- * default flow_depth K = 1, L = 1, x_size = y_size = (3,8,8)): particle (b,i) at
+ * flow_depth K in 1..4 (the reference's -K flag; default 1), L = 1, x_size = y_size = (3,8,8);
+ * L > 1 and learn_top are not supported, any other K returns NFDPF_EINVAL): the K
+ * CondGlowSteps run in sequence inside ONE launch, each with its own parameters, all
+ * conditioned on the same particle encoding; the Gaussian log-prob and the -log(256) 192
+ * constant apply once, after the last step.  Particle (b,i) at
  * x + b*x_rs + 2i, frame encoding of row b at enc + b*enc_rs (192 floats) -> the RAW
  * likelihood -nll at lik + b*lik_rs + i (the row-max shift of :301-302 is the caller's:
  * the filter's EXTERNAL-measurement phase 2, or measurement_model_cglow).
  * pe_params: particle encoder 2->16->32->192 (encoder layout above); glow_params:
- * nfdpf_cglow_params_size(K) floats (layout: nfdpf.pack.cglow_tensors). */
+ * nfdpf_cglow_params_size(K) = K * 7980 floats, step k's parameters at k * 7980 (per-step
+ * layout: csrc/cglow.hpp, packed by nfdpf.pack.cglow_tensors); -1 for K outside 1..4. */
 NFDPF_API int64_t nfdpf_cglow_params_size(int K);
 NFDPF_API int nfdpf_cglow_measurement(const float *pe_params, const float *glow_params, int K,
                             const float *enc, int64_t enc_rs, const float *x, int64_t x_rs,
                             int B, int N, float *lik, int64_t lik_rs, void *stream);
 
 /* CondGlowModel.forward(x, y) (nf/cglow/CGlowModel.py:167-176) with the reference's default
- * configuration (K = 1, L = 1, learn_top off, 256 bins): x [M,3,8,8] the condition, y [M,3,8,8]
- * the flow input, both per sample -> z [M,12,4,4] (NULL: not written) and nll [M]
+ * configuration at flow_depth K in 1..4 (L = 1, learn_top off, 256 bins): x [M,3,8,8] the
+ * condition, y [M,3,8,8] the flow input, both per sample -> z [M,12,4,4], the last step's
+ * output (NULL: not written), and nll [M]
  * (= -(log-det + Gaussian log-prob) / (192 log 2)).  glow_params as nfdpf_cglow_measurement. */
 NFDPF_API int nfdpf_cglow_flow(const float *glow_params, int K, const float *x, const float *y, int64_t M,
                                float *z, float *nll, void *stream);
@@ -289,14 +295,19 @@ NFDPF_API int nfdpf_cglow_flow(const float *glow_params, int K, const float *x, 
 /* Backward of the two CGLOW entry points above (training; the autograd
  * gradient of nf/cglow/modules.py + CGlowModel.py:167-176, d log|det W| / dW = W^-T).
  * Deterministic (fixed-order per-workgroup partials in the workspace, reduced in order).
+ * K in 1..4 as the forward entry points; K > 1 runs one launch per step from the last step to
+ * the first (the steps' inputs recomputed by one forward launch into the workspace), the
+ * condition's gradient summed over the steps in that order; g_glow has the K-step blob layout.
  *   nfdpf_cglow_measurement_backward: inputs as nfdpf_cglow_measurement, g_lik (b, i) at
  *     g_lik + b*glik_rs + i = dL/d(raw lik) -> g_x [B, N, 2], g_y [B*N, 192] = dL/d(frame
  *     encoding) per particle (the caller sums each row's N), g_glow (glow blob layout),
  *     g_pe (encoder blob layout).
  *   nfdpf_cglow_flow_backward: inputs as nfdpf_cglow_flow, g_z [M, 192] (NULL = 0), g_nll [M]
  *     -> g_x, g_y [M, 192], g_glow.
- *   workspace: nfdpf_cglow_backward_workspace(B*N or M) bytes. */
+ *   workspace: nfdpf_cglow_backward_workspace_k(B*N or M, K) bytes (K > 1: plus (K + 3)
+ *     buffers of M * 192 floats); nfdpf_cglow_backward_workspace(M) is the K = 1 size. */
 NFDPF_API int64_t nfdpf_cglow_backward_workspace(int64_t M);
+NFDPF_API int64_t nfdpf_cglow_backward_workspace_k(int64_t M, int K);
 NFDPF_API int nfdpf_cglow_measurement_backward(const float *pe_params, const float *glow_params, int K,
                                                const float *enc, int64_t enc_rs, const float *x, int64_t x_rs,
                                                int B, int N, const float *g_lik, int64_t glik_rs, float *g_x,

@@ -172,7 +172,7 @@ class DPF(nn.Module):
 
     def _fused_supported(self):
         if self.measurement == "CGLOW":
-            return self.hidden_size == 192 and getattr(self.param, "flow_depth", 1) == 1
+            return self.hidden_size == 192 and 1 <= getattr(self.param, "flow_depth", 1) <= 4
         return self.measurement in ("cos", "CRNVP", "NN", "gaussian") and self.hidden_size == 32
 
     def filtering_pos(self, obs, start_state_vs, vel_input):

@@ -2,12 +2,14 @@
 // nf/cglow/CGlowModel.py:123-176 and nf/cglow/modules.py), BASELINE config 5.
 //
 // Per particle: x = particle_encoder(pos) reshaped (3,8,8); y = this row's frame encoding
-// (3,8,8), squeezed to (12,4,4); one CondGlowStep (K = 1, L = 1):
+// (3,8,8), squeezed to (12,4,4); K CondGlowSteps in sequence (K in 1..4, L = 1), each with its
+// own parameters, all conditioned on the same x, step k > 0 reading step k-1's output:
 //   cond-actnorm : (logs, bias) = tanh(MLP(convs(x)))          y = (y + bias) e^logs
 //   cond-1x1conv : W (12x12)    = tanh(MLP(convs(x)))          y = W y,  + 16 log|det W|
 //   cond-affine  : h = convs(x) (3->16->6->6 at 4x4); f([h, z1]) -> (shift, scale)
 //                  z2 = (z2 + shift) sigmoid(scale + 2)
-// then nll = -(logdet + Gaussian logp) / (192 log 2) and lik = -nll (raw; the row-max
+// then (once, after the last step) nll = -(sum of the steps' logdets + Gaussian logp) /
+// (192 log 2) and lik = -nll (raw; the row-max
 // shift of :301-302 is applied by the caller -- the filter's EXTERNAL-measurement phase or
 // measurement_model_cglow).
 //
@@ -471,8 +473,12 @@ __device__ __forceinline__ void conv3x3(const float *glow, int wofs, int p, int 
 }
 
 // resize conv3, the coupling net f, the affine update of z2 and the Gaussian log-prob;
-// returns this particle's sum (over its 16 positions) of log scale + logp
-__device__ NFDPF_CG_PHASE_INLINE float phase_f(const float *glow_, int p, int q, float *zrow) {
+// returns this particle's sum (over its 16 positions) of log scale + logp.
+// TOP: the last step (the Gaussian log-prob is part of the sum); !TOP: the sum of log scale
+// alone.  KEEP: z2 goes back to S.yv next to z1, so the caller finds this step's output
+// (12 channels at this lane's position) there: the next step's input.
+template <bool TOP, bool KEEP>
+static __device__ NFDPF_CG_PHASE_INLINE float phase_f(const float *glow_, int p, int q, float *zrow) {
   const float *glow = sgpr_ptr(glow_);
   cfloat *F = wptr(glow + kOffF);
   float fin[kC];  // cat(resize_x(x), z1)
@@ -542,13 +548,14 @@ __device__ NFDPF_CG_PHASE_INLINE float phase_f(const float *glow_, int p, int q,
       zrow[c * 16 + q] = z1;
       zrow[(kCh + c) * 16 + q] = z2;
     }
+    if (KEEP) S.yv[p][q][kCh + c] = z2;
     lsum += logf(sc);
     lp += z2 * z2;
     lp += z1 * z1;
   }
   // Gaussian logp over the 12 channels at this position, plus this position's log scale,
   // summed over the particle's 16 positions (one DPP row)
-  float part = lsum - 0.5f * (lp + (float)kC * 1.8378770664093453f);
+  float part = TOP ? lsum - 0.5f * (lp + (float)kC * 1.8378770664093453f) : lsum;
   part += dpp_f<kDppXor1>(part);
   part += dpp_f<kDppXor2>(part);
   part += dpp_f<kDppHalfMirror>(part);
@@ -566,6 +573,11 @@ __device__ NFDPF_CG_PHASE_INLINE float phase_f(const float *glow_, int p, int q,
 #ifndef NFDPF_CG_WGS
 #define NFDPF_CG_WGS 3  // resident workgroups per CU (LDS 50 KB, <= 168 VGPRs); 2: 2.52 vs 2.12 ms
 #endif
+// MULTI: `nsteps` CondGlowSteps per tile (step k's parameters at glow + k * kStep), step k > 0
+// reading step k-1's output from registers; !MULTI is the K = 1 kernel (nsteps unused).
+// MID (with MULTI): the backward's forward pass -- every step's output z_k goes to
+// zout + (k * total + particle) * 192, no Gaussian term, no lik.
+template <bool MULTI, bool MID>
 __global__ __launch_bounds__(kThreads, NFDPF_CG_WGS) void cglow_kernel(const float *__restrict__ pe,
                                                             const float *__restrict__ glow,
                                                             const float *__restrict__ enc,
@@ -573,7 +585,8 @@ __global__ __launch_bounds__(kThreads, NFDPF_CG_WGS) void cglow_kernel(const flo
                                                             int64_t x_rs, int B, int N,
                                                             float *__restrict__ lik, int64_t lik_rs,
                                                             const float *__restrict__ xin,
-                                                            float *__restrict__ zout, float out_sign) {
+                                                            float *__restrict__ zout, float out_sign,
+                                                            int nsteps) {
   const int tid = threadIdx.x, w = tid >> 6, l = tid & 63;
   const int64_t total = (int64_t)B * N;
   const int64_t ntiles = (total + kTileP - 1) / kTileP;
@@ -581,7 +594,8 @@ __global__ __launch_bounds__(kThreads, NFDPF_CG_WGS) void cglow_kernel(const flo
   // the coupling net's per-channel scales exp(logs) (Conv2dNormy, nf/cglow/modules.py:214) and exp(3 logs)
   // (Conv2dZerosy, :233), once per launch (ordered before use by the tile's first SYNC)
   if (tid <= kC) S.zrow[tid] = 0.f;  // read-only from here (ordered by the tile's first SYNC)
-  if (tid < 2 * kYH + kC) {
+  // (MULTI: per step, below)
+  if (!MULTI && tid < 2 * kYH + kC) {
     const float *F = glow + kOffF;
     S.escale[tid] = tid < kYH ? expf(F[Aff::f0al + tid])
                     : tid < 2 * kYH ? expf(F[Aff::f2al + tid - kYH])
@@ -605,7 +619,7 @@ __global__ __launch_bounds__(kThreads, NFDPF_CG_WGS) void cglow_kernel(const flo
     // weights from the caches instead of hoisting every one of them out of the tile loop
     const float *gw = glow, *pe_ = pe;
     asm volatile("" : "+s"(gw), "+s"(pe_));
-    const float *gA = gw + kOffA, *gI = gw + kOffI;
+    const float *gA0 = gw + kOffA, *gI0 = gw + kOffI;
     // encoder weights (nfdpf.pack.encoder_tensors)
     const float *pw1 = pe_, *pb1 = pe_ + kPeB1, *pw2 = pe_ + kPeW2, *pb2 = pe_ + kPeB2, *pw3 = pe_ + kPeW3,
                 *pb3 = pe_ + kPeW3 + kE * kPeH2;
@@ -668,6 +682,23 @@ __global__ __launch_bounds__(kThreads, NFDPF_CG_WGS) void cglow_kernel(const flo
       SYNC();
     }
     CGTRACE(1)
+    const int ksteps = MULTI ? nsteps : 1;
+    float ldacc = 0.f;  // MULTI: the steps' log-dets so far
+    // (a do-while whose back edge is compile-time false without MULTI: the K = 1 kernel has
+    // no loop here, and compiles to the code it had before the steps became a loop)
+    int k = 0;
+#pragma unroll 1
+    do {
+    const float *gs = MULTI ? gw + k * kStep : gw;  // this step's parameters (wave-uniform)
+    const float *gA = MULTI ? gs + kOffA : gA0, *gI = MULTI ? gs + kOffI : gI0;
+    if (MULTI && tid < 2 * kYH + kC) {
+      // this step's coupling scales (the previous step's readers are behind a SYNC; ordered
+      // before phase_f by the conditioning nets' SYNCs)
+      const float *F = gs + kOffF;
+      S.escale[tid] = tid < kYH ? expf(F[Aff::f0al + tid])
+                      : tid < 2 * kYH ? expf(F[Aff::f2al + tid - kYH])
+                                      : expf(F[Aff::f4l + tid - 2 * kYH] * 3.0f);
+    }
     // ---- conditioning nets, conv1 (3 -> 8, 2x2 stride 2, 8x8 -> 4x4) for actnorm (A) and
     //      1x1-conv (I) nets: VALU, lane = (particle, 4x4 position)
     // This wave's B operands (weights) and epilogue biases of the conditioning nets' MFMA
@@ -809,11 +840,23 @@ __global__ __launch_bounds__(kThreads, NFDPF_CG_WGS) void cglow_kernel(const flo
     phase_y(yq, p, q);
     WSYNC();
     CGTRACE(7)
-    phase_resize(gw, p, q);
+    phase_resize(gs, p, q);
     WSYNC();
     CGTRACE(8)
     const int64_t gi = g0 + p;
-    const float part = phase_f(gw, p, q, zout && gi < total ? zout + gi * kE : nullptr);
+    if (MULTI && (MID || k + 1 < ksteps)) {
+      // not the last step: its output (left in S.yv) is the next step's input, carried in
+      // registers across the conditioning nets, whose activations share S.yv's storage
+      const float lds = phase_f<false, true>(gs, p, q, MID && gi < total ? zout + ((int64_t)k * total + gi) * kE : nullptr);
+      ldacc += S.ld[p] + lds;
+#pragma unroll
+      for (int c = 0; c < kC; ++c) yq[c] = S.yv[p][q][c];
+      if (k + 1 < ksteps) SYNC();
+      continue;
+    }
+    // the last step
+    if (MULTI) ldacc += S.ld[p];
+    const float part = phase_f<true, false>(gs, p, q, zout && gi < total ? zout + gi * kE : nullptr);
 #ifdef NFDPF_EXP_CGDUMP
     // experiment only: one particle's 1x1-conv W, its log|det W| (the LU's), actnorm outputs
     if (gi == (int64_t)NFDPF_CG_TARGET && q < 16) {
@@ -826,13 +869,14 @@ __global__ __launch_bounds__(kThreads, NFDPF_CG_WGS) void cglow_kernel(const flo
       }
     }
 #endif
-    if (q == 0 && gi < total) {
+    if (!MID && q == 0 && gi < total) {
       // logdet0 = -log(256) * 192, plus actnorm / 1x1-conv log-dets, plus this particle's sum
-      const float obj = (-5.545177444479562f * (float)kE + S.ld[p]) + part;
+      const float obj = (-5.545177444479562f * (float)kE + (MULTI ? ldacc : S.ld[p])) + part;
       const int rb = S.row[p];
       const int i = (int)(gi - (int64_t)rb * N);
       lik[rb * lik_rs + i] = out_sign * (obj / (0.6931471805599453f * (float)kE));
     }
+    } while (MULTI && ++k < ksteps);
     SYNC();
     CGTRACE(9)
   }
@@ -853,13 +897,13 @@ extern "C" NFDPF_API int nfdpf_exp_cgtrace_read(void *host) {
 }
 #endif
 
-extern "C" int64_t nfdpf_cglow_params_size(int K) { return K == 1 ? (int64_t)kStep : -1; }
+extern "C" int64_t nfdpf_cglow_params_size(int K) { return K >= 1 && K <= kMaxK ? (int64_t)K * kStep : -1; }
 
 extern "C" int nfdpf_cglow_measurement(const float *pe_params, const float *glow_params, int K,
                                        const float *enc, int64_t enc_rs, const float *x, int64_t x_rs,
                                        int B, int N, float *lik, int64_t lik_rs, void *stream) {
   NFDPF_REQUIRE(pe_params && glow_params && enc && x && lik, "nfdpf_cglow_measurement: null pointer");
-  NFDPF_REQUIRE(K == 1, "nfdpf_cglow_measurement: built for flow_depth K = 1 (got %d)", K);
+  NFDPF_REQUIRE(K >= 1 && K <= kMaxK, "nfdpf_cglow_measurement: built for flow_depth K in 1..4 (got %d)", K);
   NFDPF_REQUIRE(B >= 0 && N >= 1, "nfdpf_cglow_measurement: bad sizes");
   if (B == 0) return NFDPF_OK;
   const int64_t tiles = ((int64_t)B * N + kTileP - 1) / kTileP;
@@ -871,8 +915,12 @@ extern "C" int nfdpf_cglow_measurement(const float *pe_params, const float *glow
   // a persistent grid of exactly the resident workgroups (3 per CU: LDS 50 KB, 162 VGPRs):
   // more would start a second, late round of workgroups and leave the tail unbalanced
   const int grid = (int)std::min<int64_t>(tiles, (int64_t)cus * NFDPF_CG_WGS);
-  cglow_kernel<<<grid, kThreads, 0, as_stream(stream)>>>(pe_params, glow_params, enc, enc_rs, x, x_rs, B, N,
-                                                        lik, lik_rs, nullptr, nullptr, 1.0f);
+  if (K == 1)
+    cglow_kernel<false, false><<<grid, kThreads, 0, as_stream(stream)>>>(
+        pe_params, glow_params, enc, enc_rs, x, x_rs, B, N, lik, lik_rs, nullptr, nullptr, 1.0f, 1);
+  else
+    cglow_kernel<true, false><<<grid, kThreads, 0, as_stream(stream)>>>(
+        pe_params, glow_params, enc, enc_rs, x, x_rs, B, N, lik, lik_rs, nullptr, nullptr, 1.0f, K);
   return launch_status("nfdpf_cglow_measurement");
 }
 
@@ -888,11 +936,29 @@ static int cglow_grid(int64_t tiles) {
 extern "C" int nfdpf_cglow_flow(const float *glow_params, int K, const float *x, const float *y, int64_t M,
                                 float *z, float *nll, void *stream) {
   NFDPF_REQUIRE(glow_params && x && y && nll, "nfdpf_cglow_flow: null pointer");
-  NFDPF_REQUIRE(K == 1, "nfdpf_cglow_flow: built for flow_depth K = 1 (got %d)", K);
+  NFDPF_REQUIRE(K >= 1 && K <= kMaxK, "nfdpf_cglow_flow: built for flow_depth K in 1..4 (got %d)", K);
   NFDPF_REQUIRE(M >= 0 && M <= (int64_t)INT32_MAX, "nfdpf_cglow_flow: bad size");
   if (M == 0) return NFDPF_OK;
   // B = M rows of N = 1 (y row m is sample m), the condition x given, out_sign -1: nll
-  cglow_kernel<<<cglow_grid((M + kTileP - 1) / kTileP), kThreads, 0, as_stream(stream)>>>(
-      glow_params, glow_params, y, kE, nullptr, 0, (int)M, 1, nll, 1, x, z, -1.0f);
+  const int grid = cglow_grid((M + kTileP - 1) / kTileP);
+  if (K == 1)
+    cglow_kernel<false, false><<<grid, kThreads, 0, as_stream(stream)>>>(glow_params, glow_params, y, kE, nullptr, 0,
+                                                                         (int)M, 1, nll, 1, x, z, -1.0f, 1);
+  else
+    cglow_kernel<true, false><<<grid, kThreads, 0, as_stream(stream)>>>(glow_params, glow_params, y, kE, nullptr, 0,
+                                                                        (int)M, 1, nll, 1, x, z, -1.0f, K);
   return launch_status("nfdpf_cglow_flow");
+}
+
+// The backward's forward pass (cglow_bwd.hip): the outputs z_0 .. z_{nsteps-1} of the first
+// `nsteps` steps, z_k of particle / sample m at zmid + (k * B * N + m) * 192 as (12, 4, 4).  xin
+// null: the measurement form (particles x through the encoder pe, y = enc row b); else the flow
+// form (enc = y [B, 192] with N = 1, the condition xin [B, 192]).
+int nfdpf::cglow_forward_mid(const float *pe, const float *glow, int nsteps, const float *enc, int64_t enc_rs,
+                             const float *x, int64_t x_rs, int B, int N, const float *xin, float *zmid,
+                             hipStream_t st) {
+  const int grid = cglow_grid(((int64_t)B * N + kTileP - 1) / kTileP);
+  cglow_kernel<true, true><<<grid, kThreads, 0, st>>>(pe, glow, enc, enc_rs, x, x_rs, B, N, nullptr, 0, xin, zmid,
+                                                      1.0f, nsteps);
+  return launch_status("cglow_forward_mid");
 }

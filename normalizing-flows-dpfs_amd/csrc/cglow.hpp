@@ -35,6 +35,11 @@ struct Aff {                   // CondAffineCoupling
 };
 constexpr int kOffA = 0, kOffI = CondA::size, kOffF = kOffI + CondI::size;
 constexpr int kStep = kOffF + Aff::size;
+constexpr int kMaxK = 4;  // flow depths the kernels take: the blob holds K steps, step k at k * kStep
 
 }  // namespace cg
+
+// cglow.hip, for the K > 1 backward (cglow_bwd.hip): the first `nsteps` steps' outputs
+int cglow_forward_mid(const float *pe, const float *glow, int nsteps, const float *enc, int64_t enc_rs,
+                      const float *x, int64_t x_rs, int B, int N, const float *xin, float *zmid, hipStream_t st);
 }  // namespace nfdpf

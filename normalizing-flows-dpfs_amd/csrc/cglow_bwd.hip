@@ -3,7 +3,14 @@
 // nf/cglow/modules.py (CondActNorm :76-132, Cond1x1Conv :136-211 with the slogdet of :165,
 // CondAffineCoupling :258-303, Conv2dResize / Zeros / Normy / Zerosy :38-253, LinearZeros /
 // Norm, GaussianDiag :377-403) and of the particle encoder (model/models.py:141-150), for the
-// configuration cglow.hip is built for (K = 1, L = 1, 3x8x8 x and y, learn_top off).
+// configuration cglow.hip is built for (K in 1..4, L = 1, 3x8x8 x and y, learn_top off).
+//
+// K > 1 is a chain of per-step launches of the same kernel, from the last step down to the
+// first (launch_chain below): one forward launch (cglow.hip, cglow_forward_mid) leaves every
+// step's input z_k in the workspace; the launch of step k recomputes that step from its input,
+// takes dL/dz_k from the launch above and hands dL/dz_{k-1} to the one below, and adds its
+// share of the condition's gradient to the running sum -- step K-1 first, then downwards, one
+// owner thread per element: deterministic.  The parameter accumulators stay one step's worth.
 //
 // One workgroup = 4 waves = a tile of 16 particles (persistent over tiles), lane = (particle
 // tid / 16, 4x4 position tid % 16) as in the forward.  Per tile:
@@ -229,11 +236,20 @@ __device__ __forceinline__ bool in4(int r, int s) { return r >= 0 && r < 4 && s 
 // !PART (CondGlowModel.forward): x = xin [M, 192], y [M, 192] per sample, upstream g_nll [M] and
 // optionally g_z [M, 192].  Outputs: g_y [M, 192] per sample / particle, g_x (PART: [M, 2]
 // particles; else [M, 192]), and this workgroup's parameter-gradient row of `partial`.
-template <bool PART>
+// K = 1 is <PART, false, true>.  In a K > 1 chain `glow` is the step's slice of the blob and
+//   SQZ (steps k > 0): the step's input is the step below's output, already (12, 4, 4), at
+//     enc + m * 192 per particle / sample; g_y (dL/d input) is written in that layout too, and
+//     the condition's gradient goes out as [M, 192] to g_x (no particle-encoder backward, PART
+//     or not: that runs once, in the launch of step 0);
+//   !TOP (steps k < K-1): no Gaussian term -- the incoming gradient is g_z [M, 192] from the
+//     step above plus the upstream weight on this step's log-det -- and the condition's
+//     gradient starts from gx_in [M, 192], the sum over the steps above.
+template <bool PART, bool SQZ, bool TOP>
 __global__ __launch_bounds__(kThreads, 1) void cglow_bwd_kernel(
     const float *__restrict__ pe_, const float *__restrict__ glow, const float *__restrict__ enc, int64_t enc_rs,
     const float *__restrict__ x, int64_t x_rs, int B, int N, const float *__restrict__ g_up, int64_t gup_rs,
-    const float *__restrict__ g_z, float *__restrict__ g_y, float *__restrict__ g_x, float *__restrict__ partial) {
+    const float *__restrict__ g_z, float *__restrict__ g_y, float *__restrict__ g_x, float *__restrict__ partial,
+    const float *__restrict__ gx_in) {
   extern __shared__ __attribute__((aligned(16))) char lds_raw[];
   BLds &S = *reinterpret_cast<BLds *>(lds_raw);
   const int tid = threadIdx.x, p = tid >> 4, q = tid & 15, qi = q >> 2, qj = q & 3;
@@ -283,14 +299,15 @@ __global__ __launch_bounds__(kThreads, 1) void cglow_bwd_kernel(
     // ---------------- forward recompute ----------------
     float yq[kC];  // squeezed y at position q: channel c * 4 + f
     {
-      const float *yr = PART ? enc + (int64_t)rowb * enc_rs : enc + m * kE;
+      const float *yr = PART && !SQZ ? enc + (int64_t)rowb * enc_rs : enc + m * kE;
 #pragma unroll
       for (int c = 0; c < 3; ++c)
 #pragma unroll
-        for (int f = 0; f < 4; ++f) yq[c * 4 + f] = yr[c * 64 + (2 * qi + (f >> 1)) * 8 + 2 * qj + (f & 1)];
+        for (int f = 0; f < 4; ++f)
+          yq[c * 4 + f] = SQZ ? yr[(c * 4 + f) * 16 + q] : yr[c * 64 + (2 * qi + (f >> 1)) * 8 + 2 * qj + (f & 1)];
     }
 #pragma unroll
-    for (int k = 0; k < kE / 16; ++k) S.gX[p][q + 16 * k] = 0.f;
+    for (int k = 0; k < kE / 16; ++k) S.gX[p][q + 16 * k] = TOP ? 0.f : (valid ? gx_in[m * kE + q + 16 * k] : 0.f);
     if (PART) {
       const int i = (int)(m - (int64_t)rowb * N);
       if (q < 2) S.pxy[p][q] = x[(int64_t)rowb * x_rs + 2 * i + q];
@@ -635,12 +652,12 @@ __global__ __launch_bounds__(kThreads, 1) void cglow_bwd_kernel(
       const float shift = h[2 * c], sc = sigm(h[2 * c + 1] + 2.0f);
       const float z1 = yw[c], z2 = yw[kCh + c], z2p = (z2 + shift) * sc;
       float ez1 = 0.f, ez2 = 0.f;
-      if (!PART && g_z && valid) {
+      if ((!PART || !TOP) && g_z && valid) {
         ez1 = g_z[m * kE + c * 16 + q];
         ez2 = g_z[m * kE + (kCh + c) * 16 + q];
       }
-      gz1[c] = fmaf(-z1, gobj, ez1);
-      const float gz2p = fmaf(-z2p, gobj, ez2);
+      gz1[c] = TOP ? fmaf(-z1, gobj, ez1) : ez1;
+      const float gz2p = TOP ? fmaf(-z2p, gobj, ez2) : ez2;
       gz2[c] = gz2p * sc;
       const float gsh = gz2p * sc;
       const float gsp = gz2p * (z2 + shift) * sc * (1.0f - sc) + gobj * (1.0f - sc);
@@ -1041,7 +1058,7 @@ __global__ __launch_bounds__(kThreads, 1) void cglow_bwd_kernel(
 #pragma unroll
       for (int c = 0; c < kC; ++c) {
         const float gy0 = gya[c] * expf(S.an[p][c]);
-        if (valid) gyr[(c >> 2) * 64 + (2 * qi + ((c & 3) >> 1)) * 8 + 2 * qj + (c & 1)] = gy0;
+        if (valid) gyr[SQZ ? c * 16 + q : (c >> 2) * 64 + (2 * qi + ((c & 3) >> 1)) * 8 + 2 * qj + (c & 1)] = gy0;
         const float gls = row16_sum(gya[c] * S.ya[p][q][c]), gb = row16_sum(gy0);
         if (q == 0) {
           S.gan[p][c] = fmaf(16.0f, gobj, gls);
@@ -1276,7 +1293,7 @@ __global__ __launch_bounds__(kThreads, 1) void cglow_bwd_kernel(
     __syncthreads();
     CBT(11);
     // ---------------- the condition's gradient: out, or through the particle encoder ----------------
-    if (!PART) {
+    if (!PART || SQZ) {
       if (valid)
 #pragma unroll
         for (int k = 0; k < kE / 16; ++k) g_x[m * kE + q + 16 * k] = S.gX[p][q + 16 * k];
@@ -1391,7 +1408,7 @@ __global__ __launch_bounds__(kThreads, 1) void cglow_bwd_kernel(
                  [=](int m, int n) { return (isI ? kOffI + CondI::l4w : kOffA + CondA::l4w) + (m0 + m) * kXS + n; });
     }
   }
-  if (PART)
+  if (PART)  // (zeros from a SQZ launch: its reduce does not write g_pe)
 #pragma unroll
     for (int jj = 0; jj < 6; ++jj) {
       const int j = w + 4 * jj, mt = j >> 1, kt = j & 1;
@@ -1438,18 +1455,65 @@ static int bwd_grid(int64_t M) {
   return (int)std::max<int64_t>(1, std::min<int64_t>(tiles, kBwdGrid));
 }
 
+template <bool PART, bool SQZ, bool TOP>
+static void launch_step(int grid, const float *pe, const float *glow, const float *enc, int64_t enc_rs,
+                        const float *x, int64_t x_rs, int B, int N, const float *g_up, int64_t gup_rs,
+                        const float *g_z, float *g_y, float *g_x, const float *gx_in, float *g_glow, float *g_pe,
+                        float *partial, hipStream_t st) {
+  const size_t lds = sizeof(BLds);
+  ensure_max_dynamic_lds((const void *)cglow_bwd_kernel<PART, SQZ, TOP>, (int)lds);
+  cglow_bwd_kernel<PART, SQZ, TOP><<<grid, kThreads, lds, st>>>(pe, glow, enc, enc_rs, x, x_rs, B, N, g_up, gup_rs,
+                                                                g_z, g_y, g_x, partial, gx_in);
+  cglow_param_reduce_kernel<<<(kTotParams + 255) / 256, 256, 0, st>>>(partial, grid, g_glow, g_pe);
+}
+
 template <bool PART>
 static int launch_bwd(const float *pe, const float *glow, const float *enc, int64_t enc_rs, const float *x,
                       int64_t x_rs, int B, int N, const float *g_up, int64_t gup_rs, const float *g_z, float *g_y,
                       float *g_x, float *g_glow, float *g_pe, void *ws, hipStream_t st) {
+  launch_step<PART, false, true>(bwd_grid((int64_t)B * N), pe, glow, enc, enc_rs, x, x_rs, B, N, g_up, gup_rs, g_z,
+                                 g_y, g_x, nullptr, g_glow, g_pe, (float *)ws, st);
+  return launch_status("cglow_backward");
+}
+
+// Workspace of a K-step backward (floats): the partial rows, then for K > 1 the step inputs
+// z_0 .. z_{K-2} and two [M, 192] hand-over buffers each for dL/dz and the condition's gradient
+// (the launch of step k reads what the launch of step k+1 wrote, and writes the other one).
+static int64_t partial_floats(int64_t M) { return ((int64_t)bwd_grid(M) * kTotParams + 63) / 64 * 64; }
+static int64_t workspace_floats(int64_t M, int K) {
+  return K == 1 ? (int64_t)bwd_grid(M) * kTotParams : partial_floats(M) + (int64_t)(K - 1 + 4) * M * kE;
+}
+
+// K > 1: one launch per step, step K-1 first.  In the measurement form (PART) the condition's
+// gradient of steps k > 0 is the [M, 192] encoding gradient; the launch of step 0 adds its own
+// and runs the particle encoder's backward once, on the sum.
+template <bool PART>
+static int launch_chain(const float *pe, const float *glow, int K, const float *enc, int64_t enc_rs, const float *x,
+                        int64_t x_rs, int B, int N, const float *g_up, int64_t gup_rs, const float *g_z, float *g_y,
+                        float *g_x, float *g_glow, float *g_pe, void *ws, hipStream_t st) {
   const int64_t M = (int64_t)B * N;
   const int grid = bwd_grid(M);
-  const size_t lds = sizeof(BLds);
-  ensure_max_dynamic_lds((const void *)cglow_bwd_kernel<PART>, (int)lds);
-  float *partial = (float *)ws;
-  cglow_bwd_kernel<PART><<<grid, kThreads, lds, st>>>(pe, glow, enc, enc_rs, x, x_rs, B, N, g_up, gup_rs, g_z, g_y,
-                                                      g_x, partial);
-  cglow_param_reduce_kernel<<<(kTotParams + 255) / 256, 256, 0, st>>>(partial, grid, g_glow, g_pe);
+  float *partial = (float *)ws, *zmid = partial + partial_floats(M);
+  float *gzb[2] = {zmid + (int64_t)(K - 1) * M * kE, zmid + (int64_t)K * M * kE};
+  float *gxb[2] = {zmid + (int64_t)(K + 1) * M * kE, zmid + (int64_t)(K + 2) * M * kE};
+  const int rc = PART ? cglow_forward_mid(pe, glow, K - 1, enc, enc_rs, x, x_rs, B, N, nullptr, zmid, st)
+                      : cglow_forward_mid(glow, glow, K - 1, enc, enc_rs, nullptr, 0, B, N, x, zmid, st);
+  if (rc != NFDPF_OK) return rc;
+  for (int k = K - 1; k >= 0; --k) {
+    const int cur = (K - 1 - k) & 1;
+    const float *gl = glow + (int64_t)k * kStep;
+    float *gg = g_glow + (int64_t)k * kStep;
+    const float *zin = k > 0 ? zmid + (int64_t)(k - 1) * M * kE : nullptr;
+    if (k == K - 1)
+      launch_step<PART, true, true>(grid, pe, gl, zin, kE, x, x_rs, B, N, g_up, gup_rs, g_z, gzb[cur], gxb[cur],
+                                    nullptr, gg, nullptr, partial, st);
+    else if (k > 0)
+      launch_step<PART, true, false>(grid, pe, gl, zin, kE, x, x_rs, B, N, g_up, gup_rs, gzb[cur ^ 1], gzb[cur],
+                                     gxb[cur], gxb[cur ^ 1], gg, nullptr, partial, st);
+    else
+      launch_step<PART, false, false>(grid, pe, gl, enc, enc_rs, x, x_rs, B, N, g_up, gup_rs, gzb[cur ^ 1], g_y, g_x,
+                                      gxb[cur ^ 1], gg, g_pe, partial, st);
+  }
   return launch_status("cglow_backward");
 }
 
@@ -1469,22 +1533,31 @@ extern "C" int64_t nfdpf_cglow_backward_workspace(int64_t M) {
   return (int64_t)cgb::bwd_grid(M) * cgb::kTotParams * (int64_t)sizeof(float);
 }
 
+extern "C" int64_t nfdpf_cglow_backward_workspace_k(int64_t M, int K) {
+  if (M < 0 || K < 1 || K > cg::kMaxK) return -1;
+  return cgb::workspace_floats(M, K) * (int64_t)sizeof(float);
+}
+
 extern "C" int nfdpf_cglow_measurement_backward(const float *pe_params, const float *glow_params, int K,
                                                 const float *enc, int64_t enc_rs, const float *x, int64_t x_rs,
                                                 int B, int N, const float *g_lik, int64_t glik_rs, float *g_x,
                                                 float *g_y, float *g_glow, float *g_pe, void *workspace,
                                                 void *stream) {
-  NFDPF_REQUIRE(K == 1, "nfdpf_cglow_measurement_backward: built for flow_depth K = 1 (got %d)", K);
+  NFDPF_REQUIRE(K >= 1 && K <= cg::kMaxK, "nfdpf_cglow_measurement_backward: built for flow_depth K in 1..4 (got %d)",
+                K);
   NFDPF_REQUIRE(B >= 0 && N >= 1, "nfdpf_cglow_measurement_backward: bad sizes");
   NFDPF_REQUIRE(g_glow && g_pe, "nfdpf_cglow_measurement_backward: null pointer");
   hipStream_t st = as_stream(stream);
   if (B == 0) {
-    (void)hipMemsetAsync(g_glow, 0, sizeof(float) * cg::kStep, st);
+    (void)hipMemsetAsync(g_glow, 0, sizeof(float) * cg::kStep * K, st);
     (void)hipMemsetAsync(g_pe, 0, sizeof(float) * cgb::kPeE, st);
     return launch_status("nfdpf_cglow_measurement_backward");
   }
   NFDPF_REQUIRE(pe_params && glow_params && enc && x && g_lik && g_x && g_y && workspace,
                 "nfdpf_cglow_measurement_backward: null pointer");
+  if (K > 1)
+    return cgb::launch_chain<true>(pe_params, glow_params, K, enc, enc_rs, x, x_rs, B, N, g_lik, glik_rs, nullptr,
+                                   g_y, g_x, g_glow, g_pe, workspace, st);
   return cgb::launch_bwd<true>(pe_params, glow_params, enc, enc_rs, x, x_rs, B, N, g_lik, glik_rs, nullptr, g_y,
                                g_x, g_glow, g_pe, workspace, as_stream(stream));
 }
@@ -1492,15 +1565,18 @@ extern "C" int nfdpf_cglow_measurement_backward(const float *pe_params, const fl
 extern "C" int nfdpf_cglow_flow_backward(const float *glow_params, int K, const float *x, const float *y, int64_t M,
                                          const float *g_z, const float *g_nll, float *g_x, float *g_y,
                                          float *g_glow, void *workspace, void *stream) {
-  NFDPF_REQUIRE(K == 1, "nfdpf_cglow_flow_backward: built for flow_depth K = 1 (got %d)", K);
+  NFDPF_REQUIRE(K >= 1 && K <= cg::kMaxK, "nfdpf_cglow_flow_backward: built for flow_depth K in 1..4 (got %d)", K);
   NFDPF_REQUIRE(M >= 0 && M <= (int64_t)INT32_MAX, "nfdpf_cglow_flow_backward: bad size");
   NFDPF_REQUIRE(g_glow, "nfdpf_cglow_flow_backward: null pointer");
   hipStream_t st = as_stream(stream);
   if (M == 0) {
-    (void)hipMemsetAsync(g_glow, 0, sizeof(float) * cg::kStep, st);
+    (void)hipMemsetAsync(g_glow, 0, sizeof(float) * cg::kStep * K, st);
     return launch_status("nfdpf_cglow_flow_backward");
   }
   NFDPF_REQUIRE(glow_params && x && y && g_nll && g_x && g_y && workspace, "nfdpf_cglow_flow_backward: null pointer");
+  if (K > 1)
+    return cgb::launch_chain<false>(nullptr, glow_params, K, y, cg::kE, x, 0, (int)M, 1, g_nll, 1, g_z, g_y, g_x,
+                                    g_glow, nullptr, workspace, st);
   return cgb::launch_bwd<false>(nullptr, glow_params, y, cg::kE, x, 0, (int)M, 1, g_nll, 1, g_z, g_y, g_x, g_glow,
                                 nullptr, workspace, st);
 }

@@ -361,7 +361,7 @@ class _CglowRunner:
         m = self.model
         pe = blob(m, "pe", m.particle_encoder, lambda: encoder_tensors(m.particle_encoder), x.device)
         glow = blob(m, "glow", m.CGLOW, lambda: cglow_tensors(m.CGLOW), x.device)
-        return (_ops.cglow_measurement(pe, glow, enc.float(), x.float()),)
+        return (_ops.cglow_measurement(pe, glow, enc.float(), x.float(), K=m.CGLOW.flow.K),)
 
     def torch(self, enc, x):
         return (self.model.torch_forward_raw(enc, x),)
@@ -377,7 +377,8 @@ class _CglowRunner:
         pe = blob(m, "pe", m.particle_encoder, lambda: encoder_tensors(m.particle_encoder), x.device)
         glow = blob(m, "glow", m.CGLOW, lambda: cglow_tensors(m.CGLOW), x.device)
         g = gouts[0] if gouts[0] is not None else torch.zeros(x.shape[:2], device=x.device)
-        g_enc, gx, g_glow, g_pe = _ops.cglow_measurement_backward(pe, glow, enc.float(), x.float(), g.float())
+        g_enc, gx, g_glow, g_pe = _ops.cglow_measurement_backward(pe, glow, enc.float(), x.float(), g.float(),
+                                                                  K=m.CGLOW.flow.K)
         pe_params, gl_params = list(m.particle_encoder.parameters()), list(m.CGLOW.parameters())
         res = blob_param_grads(m, "pe_grad", pe_params, lambda get: encoder_tensors(m.particle_encoder, get), g_pe)
         res += blob_param_grads(m, "glow_grad", gl_params, lambda get: cglow_tensors(m.CGLOW, get), g_glow)
@@ -399,7 +400,7 @@ class measurement_model_cglow(nn.Module):
         gradients through the recompute backward of _CglowRunner."""
         if not self.CGLOW.kernel_supported():
             raise NfdpfError("measurement_model_cglow: the HIP kernel is built for the reference's default CGLOW "
-                             "(K = 1, L = 1, 3x8x8, learn_top off, 256 bins)")
+                             "with flow_depth K in 1..4 (L = 1, 3x8x8, learn_top off, 256 bins)")
         lik = _ag.apply(_CglowRunner(self), (encodings, update_particles), list(self.parameters()))[0]
         return lik - lik.max(dim=-1, keepdim=True)[0]
 

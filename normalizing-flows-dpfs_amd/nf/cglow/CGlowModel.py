@@ -4,7 +4,7 @@ keys (flow.layers.{k}...., new_mean, new_logs), same forward / reverse API.
 ``CondGlowModel.forward(x, y)`` -- the likelihood the DPF's CGLOW measurement evaluates (squeeze
 -> K x [cond-actnorm, cond-1x1 conv with a per-sample 12x12 slogdet, cond-affine coupling] ->
 Gaussian log-prob, CGlowModel.py:167-176) -- runs as one HIP kernel (csrc/cglow.hip,
-nfdpf_cglow_flow) for the configuration the reference's flags give (K = 1, L = 1, x_size =
+nfdpf_cglow_flow) for the configuration the reference's flags give (K in 1..4, L = 1, x_size =
 y_size = (3, 8, 8), learn_top off) and returns the reference's (z, nll).  Under autograd its
 backward differentiates ``torch_forward``, a PyTorch restatement of the same math run on the
 saved inputs (nfdpf.autograd; the forward value is the kernel's).  ``reverse=True`` (sampling;
@@ -86,7 +86,7 @@ class _FlowRunner:
         from nfdpf.pack import blob, cglow_tensors
         m = self.model
         glow = blob(m, "glow", m, lambda: cglow_tensors(m), x.device)
-        return ops.cglow_flow(glow, x, y)
+        return ops.cglow_flow(glow, x, y, K=m.flow.K)
 
     def torch(self, x, y):
         return self.model.torch_forward(x, y)
@@ -98,7 +98,7 @@ class _FlowRunner:
         m = self.model
         glow = blob(m, "glow", m, lambda: cglow_tensors(m), x.device)
         g_z, g_nll = gouts
-        gx, gy, g_glow = ops.cglow_flow_backward(glow, x, y, g_z, g_nll)
+        gx, gy, g_glow = ops.cglow_flow_backward(glow, x, y, g_z, g_nll, K=m.flow.K)
         res = blob_param_grads(m, "glow_grad", list(m.parameters()), lambda get: cglow_tensors(m, get), g_glow)
         return (gx, gy), res
 
@@ -123,9 +123,10 @@ class CondGlowModel(nn.Module):
 
     def kernel_supported(self) -> bool:
         """The configuration csrc/cglow.hip is built for: the reference's defaults
-        (arguments.py:61-70) K = 1, L = 1, 3x8x8 x and y, hidden 8 / 16 / 8, learn_top off."""
+        (arguments.py:61-70) with flow_depth K in 1..4: L = 1, 3x8x8 x and y, hidden 8 / 16 / 8,
+        learn_top off."""
         f = self.flow
-        return (f.K == 1 and f.L == 1 and not self.learn_top and float(self.n_bins) == 256.0
+        return (1 <= f.K <= 4 and f.L == 1 and not self.learn_top and float(self.n_bins) == 256.0
                 and list(f.output_shapes[-1][1:]) == [12, 4, 4])
 
     def forward(self, x=0.0, y=None, eps_std=1.0, reverse=False):
@@ -139,7 +140,7 @@ class CondGlowModel(nn.Module):
                     y = modules.GaussianDiag.batchsample(x.size(0), mean, logs, eps_std)
                 return self.flow(x, y, eps_std=eps_std, reverse=True)
         if not self.kernel_supported():
-            raise NfdpfError("CondGlowModel.forward: the HIP kernel is built for K = 1, L = 1, 3x8x8 inputs, "
+            raise NfdpfError("CondGlowModel.forward: the HIP kernel is built for K in 1..4, L = 1, 3x8x8 inputs, "
                              "learn_top off and 256 bins (the reference's defaults)")
         z, nll = _ag.apply(_FlowRunner(self), (x.float().contiguous(), y.float().contiguous()),
                            list(self.parameters()))

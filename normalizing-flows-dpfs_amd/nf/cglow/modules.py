@@ -2,7 +2,7 @@
 structure and initialisation of each layer, so checkpoints keep their state_dict keys, and
 each layer's forward / reverse in PyTorch.
 
-The likelihood evaluation the DPF runs (CondGlowModel.forward, K = 1, L = 1) is ONE HIP kernel
+The likelihood evaluation the DPF runs (CondGlowModel.forward, K in 1..4, L = 1) is ONE HIP kernel
 (csrc/cglow.hip).  The PyTorch forwards below are not on that path: they are what autograd
 differentiates when CGLOW is trained (nfdpf.autograd re-runs them on the saved inputs, the
 forward value still being the kernel's) and the reverse (sampling) direction, which the DPF

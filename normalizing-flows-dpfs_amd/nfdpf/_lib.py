@@ -114,6 +114,7 @@ SIGNATURES = {
                                         c_int, c_void_p, c_int64, c_void_p]),
     "nfdpf_cglow_flow": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "nfdpf_cglow_backward_workspace": (c_int64, [c_int64]),
+    "nfdpf_cglow_backward_workspace_k": (c_int64, [c_int64, c_int]),
     "nfdpf_cglow_measurement_backward": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_int64,
                                                  c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
                                                  c_void_p, c_void_p, c_void_p]),

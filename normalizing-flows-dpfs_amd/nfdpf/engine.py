@@ -824,7 +824,7 @@ class FilterEngine:
                 step()
                 if ev is not None:
                     ev.record_start(dev)  # the CGLOW kernel is the step's dominant launch
-                ops.cglow_measurement(pe, meas, enc[:, t], hx[:, t], out=lik_ext)
+                ops.cglow_measurement(pe, meas, enc[:, t], hx[:, t], K=self.m.cglow_measurement.flow.K, out=lik_ext)
                 if ev is not None:
                     ev.record_end(dev)
                 d.phase = 2

@@ -448,7 +448,7 @@ def cglow_measurement_backward(pe_blob, glow_blob, enc, x, g_lik, K=1):
     gy = torch.empty((B * N, 192), device=x.device, dtype=f32)
     g_glow = torch.empty_like(glow_blob)
     g_pe = torch.empty_like(pe_blob)
-    nb = int(lib().nfdpf_cglow_backward_workspace(B * N))
+    nb = int(lib().nfdpf_cglow_backward_workspace_k(B * N, int(K)))
     ws = torch.empty(max(1, nb // 4), device=x.device, dtype=f32)
     check(lib().nfdpf_cglow_measurement_backward(ptr(pe_blob), ptr(glow_blob), int(K), ptr(enc), enc.stride(0), ptr(x),
                                                  x.stride(0), B, N, ptr(g_lik), g_lik.stride(0), ptr(gx), ptr(gy),
@@ -463,12 +463,14 @@ def cglow_flow_backward(glow_blob, x, y, g_z, g_nll, K=1):
     require_device(x, "cglow_flow_backward")
     M = x.shape[0]
     x, y = _c(x), _c(y)
+    if int(glow_blob.numel()) != int(lib().nfdpf_cglow_params_size(int(K))):
+        raise L.NfdpfError("cglow_flow_backward: parameter blob does not match flow_depth K")
     g_nll = _c(g_nll) if g_nll is not None else torch.zeros((M,), device=x.device, dtype=f32)
     g_z = _c(g_z) if g_z is not None else None
     gx = torch.empty_like(x)
     gy = torch.empty_like(y)
     g_glow = torch.empty_like(glow_blob)
-    nb = int(lib().nfdpf_cglow_backward_workspace(M))
+    nb = int(lib().nfdpf_cglow_backward_workspace_k(M, int(K)))
     ws = torch.empty(max(1, nb // 4), device=x.device, dtype=f32)
     check(lib().nfdpf_cglow_flow_backward(ptr(_c(glow_blob)), int(K), ptr(x), ptr(y), int(M),
                                           ptr(g_z) if g_z is not None else None, ptr(g_nll), ptr(gx), ptr(gy),
@@ -484,6 +486,8 @@ def cglow_flow(glow_blob, x, y, K=1):
     if tuple(x.shape[1:]) != (3, 8, 8) or tuple(y.shape) != tuple(x.shape):
         raise L.NfdpfError(f"cglow_flow: x and y must both be [M, 3, 8, 8] (got {tuple(x.shape)}, {tuple(y.shape)})")
     x, y = _c(x), _c(y)
+    if int(glow_blob.numel()) != int(lib().nfdpf_cglow_params_size(int(K))):
+        raise L.NfdpfError("cglow_flow: parameter blob does not match flow_depth K")
     z = torch.empty((M, 12, 4, 4), device=x.device, dtype=f32)
     nll = torch.empty((M,), device=x.device, dtype=f32)
     check(lib().nfdpf_cglow_flow(ptr(_c(glow_blob)), int(K), ptr(x), ptr(y), int(M), ptr(z), ptr(nll),

@@ -114,24 +114,30 @@ def _cond_net_tensors(m: nn.Module, get=_same):
                                                                    l4.weight, l4.bias)]
 
 
+CGLOW_MAX_K = 4  # flow depths the CGLOW kernels take (csrc/cglow.hpp kMaxK)
+
+
 def cglow_tensors(glow: nn.Module, get=_same):
-    """CondGlowModel (nf/cglow/CGlowModel.py) with K = 1, L = 1: the CondGlowStep's actnorm
-    net, 1x1-conv net, then the affine coupling (modules.py:258-303) in the kernel layout of
-    csrc/cglow.hip (Aff): resize_x / f convolutions tap-major, output channel fastest."""
+    """CondGlowModel (nf/cglow/CGlowModel.py) with K in 1..4, L = 1: per CondGlowStep, in model
+    order (step k at k * kStep floats), the actnorm net, 1x1-conv net, then the affine coupling
+    (modules.py:258-303) in the kernel layout of csrc/cglow.hip (Aff): resize_x / f
+    convolutions tap-major, output channel fastest."""
     steps = [l for l in glow.flow.layers if hasattr(l, "affine")]
-    if len(steps) != 1:
-        raise ValueError(f"the CGLOW kernel is built for flow_depth K = 1 (got {len(steps)} steps)")
-    st = steps[0]
-    a = st.affine
-    r0, r2, r4 = [l for l in a.resize_x if isinstance(l, nn.Conv2d)]
-    f0, f2, f4 = [l for l in a.f if isinstance(l, nn.Conv2d)]
-    w2 = get(f2.weight)
-    return (_cond_net_tensors(st.actnorm, get) + _cond_net_tensors(st.invconv, get) +
-            [_taps_last(get(r0.weight)), get(r0.bias), _taps_last(get(r2.weight)), get(r2.bias),
-             _taps_last(get(r4.weight)), get(r4.bias),
-             _taps_last(get(f0.weight)), get(f0.actnorm.bias), get(f0.actnorm.logs),
-             w2.reshape(w2.shape[0], -1).t(), get(f2.actnorm.bias), get(f2.actnorm.logs),
-             _taps_last(get(f4.weight)), get(f4.bias), get(f4.logs), get(f4.newbias)])
+    if not 1 <= len(steps) <= CGLOW_MAX_K:
+        raise ValueError(f"the CGLOW kernel is built for flow_depth K in 1..{CGLOW_MAX_K} (got {len(steps)} steps)")
+    out = []
+    for st in steps:
+        a = st.affine
+        r0, r2, r4 = [l for l in a.resize_x if isinstance(l, nn.Conv2d)]
+        f0, f2, f4 = [l for l in a.f if isinstance(l, nn.Conv2d)]
+        w2 = get(f2.weight)
+        out += (_cond_net_tensors(st.actnorm, get) + _cond_net_tensors(st.invconv, get) +
+                [_taps_last(get(r0.weight)), get(r0.bias), _taps_last(get(r2.weight)), get(r2.bias),
+                 _taps_last(get(r4.weight)), get(r4.bias),
+                 _taps_last(get(f0.weight)), get(f0.actnorm.bias), get(f0.actnorm.logs),
+                 w2.reshape(w2.shape[0], -1).t(), get(f2.actnorm.bias), get(f2.actnorm.logs),
+                 _taps_last(get(f4.weight)), get(f4.bias), get(f4.logs), get(f4.newbias)])
+    return out
 
 
 def flows_tensors(flows, get=_same):
