@@ -103,7 +103,11 @@ NFDPF_API int nfdpf_cond_stack(const float *params, int n_flows, int dim, int ob
  *   blob layout of params (every entry a {t, s} pair, as nfdpf_cond_stack reads it)
  *   workspace: nfdpf_cond_stack_backward_workspace() bytes (per-workgroup parameter partials,
  *   summed in a fixed order: the result is deterministic)
- * Built for dim in {2, 4, 32}, hidden 8, n_flows 1..4, LDS-bound obser_dim (<= ~400 at dim 2). */
+ * Built for dim in {2, 4, 16, 32, 64}, hidden 8, n_flows 1..4, LDS-bound obser_dim (<= ~400 at
+ * dim 2; dim = obser_dim = 64 needs 56 + 32 n_flows KB of the 160 KB: n_flows <= 3, four are
+ * refused).  nfdpf_cond_stack_backward_supported: 1 when the call would be accepted (an instance
+ * for dim / hidden exists and the LDS bound holds), else 0; no device needed. */
+NFDPF_API int nfdpf_cond_stack_backward_supported(int n_flows, int dim, int obser_dim, int hidden);
 NFDPF_API int64_t nfdpf_cond_stack_backward_workspace(int n_flows, int dim, int obser_dim, int hidden,
                                                       int64_t rows);
 NFDPF_API int nfdpf_cond_stack_backward(const float *params, int n_flows, int dim, int obser_dim,
@@ -228,7 +232,13 @@ NFDPF_API int nfdpf_normalize_log_probs(const float *logw, int B, int N, float a
 
 /* Measurement models (model/models.py:206-278): enc [B,E] frame encodings,
  * x [B,N,2] particles -> lik [B,N].  kind = NFDPF_MEAS_*; meas_params: CRNVP stack
- * (2 flows, dim E, obser E) or likelihood_est (NN); prior_std: CRNVP prior (2.5). */
+ * (1..4 flows, dim E, obser E) or likelihood_est (NN); prior_std: CRNVP prior (2.5).
+ * E (--hiddensize): one of the built widths 16, 32, 64 (csrc/meas_widths.hpp holds the list;
+ * nfdpf_meas_width_supported asks it); any other width returns NFDPF_EINVAL, nothing launched,
+ * the message listing the built widths.  The backward entry points below take the same widths. */
+/* 1 when the measurement `kind` (NFDPF_MEAS_COS, _CRNVP, _NN, _GAUSSIAN) is built at frame-encoding
+ * width E, forward and backward; else 0.  No device needed.  No reference counterpart: a query. */
+NFDPF_API int nfdpf_meas_width_supported(int kind, int E);
 NFDPF_API int nfdpf_measurement(int kind, const float *pe_params, const float *meas_params, int n_flows,
                       const float *enc, const float *x, int B, int N, int E, float prior_std,
                       float *lik, void *stream);
@@ -238,17 +248,24 @@ NFDPF_API int nfdpf_measurement(int kind, const float *pe_params, const float *m
  * encoder :130-139, et_distance utils.py:8-15).
  *   pe_params: the same packed encoder blob; enc [B, E] frame encodings; x [B, N, 2];
  *   g_lik [B, N] = dL/dlik
- *   g_enc [B, E], g_x [B, N, 2]; g_params [1648]: the encoder's gradient in the plain
- *   nn.Linear layout W1 b1 W2 b2 W3 b3 (= the module's parameter order)
- *   workspace: nfdpf_cos_measurement_backward_workspace(B, N) bytes (fixed-order partials) */
+ *   g_enc [B, E], g_x [B, N, 2]; g_params [2*16 + 16 + 16*32 + 32 + 32*E + E] (1648 at E = 32):
+ *   the encoder's gradient in the plain nn.Linear layout W1 b1 W2 b2 W3 b3 (= the module's
+ *   parameter order)
+ *   workspace: nfdpf_cos_measurement_backward_workspace_e(B, N, E) bytes (fixed-order partials;
+ *   nfdpf_cos_measurement_backward_workspace(B, N) is the E = 32 size; -1 for a width not built) */
 /* The particle encoder alone (model/models.py:130-139), for models that feed its output on
- * (CRNVP: the flow's condition, model/models.py:256-278): mode 0 e_out [B*N, 32] = PE(x);
- * mode 1 the backward for a given g_e [B*N, 32] -> g_x [B, N, 2], g_params [1648] (nn.Linear
- * order), workspace nfdpf_cos_measurement_backward_workspace(B, N) bytes. */
+ * (CRNVP: the flow's condition, model/models.py:256-278): mode 0 e_out [B*N, E] = PE(x);
+ * mode 1 the backward for a given g_e [B*N, E] -> g_x [B, N, 2], g_params [2*16 + 16 + 16*32 +
+ * 32 + 32*E + E] (nn.Linear order), workspace nfdpf_cos_measurement_backward_workspace_e(B, N, E)
+ * bytes.  nfdpf_particle_encoder is nfdpf_particle_encoder_e at E = 32. */
 NFDPF_API int nfdpf_particle_encoder(int mode, const float *pe_params, const float *x, int B, int N,
                                      const float *g_e, float *e_out, float *g_x, float *g_params,
                                      void *workspace, void *stream);
+NFDPF_API int nfdpf_particle_encoder_e(int mode, const float *pe_params, const float *x, int B, int N, int E,
+                                       const float *g_e, float *e_out, float *g_x, float *g_params,
+                                       void *workspace, void *stream);
 NFDPF_API int64_t nfdpf_cos_measurement_backward_workspace(int B, int N);
+NFDPF_API int64_t nfdpf_cos_measurement_backward_workspace_e(int B, int N, int E);
 NFDPF_API int nfdpf_cos_measurement_backward(const float *pe_params, const float *enc, const float *x,
                                              const float *g_lik, int B, int N, int E, float *g_enc,
                                              float *g_x, float *g_params, void *workspace, void *stream);
@@ -259,10 +276,12 @@ NFDPF_API int nfdpf_cos_measurement_backward(const float *pe_params, const float
  * nfdpf_particle_encoder mode 1.
  *   meas_params: the likelihood_est blob of nfdpf_measurement (NN); enc [B, E] frame encodings;
  *   e_particles [B*N, E] = PE(x) (nfdpf_particle_encoder mode 0); g_lik [B, N]
- *   g_e [B*N, E], g_enc [B, E]; g_params [8385]: likelihood_est's gradient in the plain
- *   nn.Linear layout W1 b1 W2 b2 W3 b3
- *   workspace: nfdpf_nn_measurement_backward_workspace(B, N) bytes (fixed-order partials) */
+ *   g_e [B*N, E], g_enc [B, E]; g_params [64*2E + 64 + 64*64 + 64 + 64 + 1] (8385 at E = 32):
+ *   likelihood_est's gradient in the plain nn.Linear layout W1 b1 W2 b2 W3 b3
+ *   workspace: nfdpf_nn_measurement_backward_workspace_e(B, N, E) bytes (fixed-order partials;
+ *   nfdpf_nn_measurement_backward_workspace(B, N) is the E = 32 size; -1 for a width not built) */
 NFDPF_API int64_t nfdpf_nn_measurement_backward_workspace(int B, int N);
+NFDPF_API int64_t nfdpf_nn_measurement_backward_workspace_e(int B, int N, int E);
 NFDPF_API int nfdpf_nn_measurement_backward(const float *meas_params, const float *enc, const float *e_particles,
                                             const float *g_lik, int B, int N, int E, float *g_e, float *g_enc,
                                             float *g_params, void *workspace, void *stream);
@@ -461,6 +480,9 @@ typedef struct nfdpf_filter_desc {
                                hand-off fault as a non-resident grid does) */
   int32_t gate_world;       /* ranks in gate_peers */
   int32_t gate_rank;        /* this rank's index in gate_peers */
+  int32_t lik_ext_asis;     /* measurement EXTERNAL, phase 2: 0 = subtract the row max of lik_ext (the
+                               models that shift: CGLOW, CRNVP, gaussian; model/models.py:276,301),
+                               nonzero = take lik_ext as is (cos, NN: the reference does not shift them) */
 } nfdpf_filter_desc;
 
 NFDPF_API int nfdpf_filter_step(const nfdpf_filter_desc *d, void *stream);

@@ -26,6 +26,7 @@ from model.models import (build_conditional_glow, build_conditional_nf, build_de
                           measurement_model_cglow, measurement_model_cnf, measurement_model_cosine_distance,
                           measurement_model_Gaussian, measurement_model_NN, motion_update, nf_dynamic_model,
                           proposal_likelihood)
+from nfdpf._lib import meas_width_supported, require_meas_width
 from nfdpf.engine import FilterConfig, FilterEngine, ShardInfo
 from nfdpf.gradsync import GradBucket, global_mean, sharded_supervised_loss, world_size
 from resamplers.resamplers import resampler
@@ -57,6 +58,9 @@ class DPF(nn.Module):
         self.NFcond = args.NF_cond
         self.measurement = args.measurement
         self.hidden_size = args.hiddensize
+        if args.measurement in ("cos", "CRNVP", "NN", "gaussian"):
+            # (the HIP measurement kernels are built per width: refuse here, not inside the first step)
+            require_meas_width(args.measurement, args.hiddensize, "DPF")
         self.state_dim = 2  # particles are 2-D positions (DPFs.py:31)
         self.lr = args.lr
         self.alpha = args.alpha
@@ -173,7 +177,8 @@ class DPF(nn.Module):
     def _fused_supported(self):
         if self.measurement == "CGLOW":
             return self.hidden_size == 192 and 1 <= getattr(self.param, "flow_depth", 1) <= 4
-        return self.measurement in ("cos", "CRNVP", "NN", "gaussian") and self.hidden_size == 32
+        return self.measurement in ("cos", "CRNVP", "NN", "gaussian") and \
+            meas_width_supported(self.measurement, self.hidden_size)
 
     def filtering_pos(self, obs, start_state_vs, vel_input):
         """The T-step particle filter (DPFs.py:144-216) -> the reference's 9-tuple."""

@@ -158,6 +158,7 @@ __global__ __launch_bounds__(BLK) void filter_step_kernel(const nfdpf_filter_des
     float m = -INFINITY;
     for (int i = tid; i < N; i += BLK) m = fmaxf(m, lx[i]);
     lshift = block_max(m, L.f);
+    if (d.lik_ext_asis) lshift = 0.f;  // cos / NN supplied externally: the reference does not shift them
   } else if (MEAS == NFDPF_MEAS_CRNVP || MEAS == NFDPF_MEAS_GAUSSIAN) {
     lshift = L.bc[1];
   }

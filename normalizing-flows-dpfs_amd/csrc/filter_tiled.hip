@@ -1882,7 +1882,9 @@ __global__ __launch_bounds__(kTile) void tiled_extlik_kernel(const nfdpf_filter_
   }
   double *sm = reinterpret_cast<double *>(d.ess_out) + ((int64_t)b * tiles + tile) * kSm;
   const float m = block_max_dpp(lk, shf);
-  if (threadIdx.x == 0) sm[3] = m;
+  // (lik_ext_asis: cos / NN supplied externally are not shifted -- a row max of 0 in every tile's
+  // partial makes the normalisation's lik - Lmax the identity)
+  if (threadIdx.x == 0) sm[3] = d.lik_ext_asis ? 0.f : m;
   store_softmax(u, valid, sm, shf + 8, shd2);  // shf[0:8] held block_max
 }
 

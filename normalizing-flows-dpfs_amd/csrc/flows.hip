@@ -134,11 +134,13 @@ extern "C" int nfdpf_cond_stack(const float *params, int n_flows, int dim, int o
   NFDPF_COND(1, 8)
   NFDPF_COND(2, 8)
   NFDPF_COND(16, 8)
+  NFDPF_COND(8, 8)   // dim 16, 64: the CRNVP measurement's stack at the other built frame-encoding
+  NFDPF_COND(32, 8)  // widths (meas_widths.hpp; its backward recomputes through this entry point)
   NFDPF_COND(1, 16)
   NFDPF_COND(16, 16)
   NFDPF_COND(1, 32)
 #undef NFDPF_COND
-  set_error("nfdpf_cond_stack: unsupported (dim=%d, hidden=%d); built for dim in {2,4,32}, "
+  set_error("nfdpf_cond_stack: unsupported (dim=%d, hidden=%d); built for dim in {2,4,32} (hidden 8: also 16, 64), "
             "hidden in {8,16,32}",
             dim, hidden);
   return NFDPF_EINVAL;

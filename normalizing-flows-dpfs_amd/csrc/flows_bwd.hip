@@ -382,6 +382,20 @@ extern "C" int64_t nfdpf_cond_stack_backward_workspace(int n_flows, int dim, int
   return blocks * stack_param_floats(n_flows, dim, obser_dim, hidden) * (int64_t)sizeof(float);
 }
 
+extern "C" int nfdpf_cond_stack_backward_supported(int n_flows, int dim, int obser_dim, int hidden) {
+  if (n_flows < 1 || n_flows > kBwdMaxFlows || obser_dim < 0 || hidden != 8) return 0;
+  size_t lds;
+  switch (dim) {
+    case 2: lds = BwdLds<1, 8>::bytes(n_flows, obser_dim); break;
+    case 4: lds = BwdLds<2, 8>::bytes(n_flows, obser_dim); break;
+    case 16: lds = BwdLds<8, 8>::bytes(n_flows, obser_dim); break;
+    case 32: lds = BwdLds<16, 8>::bytes(n_flows, obser_dim); break;
+    case 64: lds = BwdLds<32, 8>::bytes(n_flows, obser_dim); break;
+    default: return 0;
+  }
+  return lds <= 160 * 1024 ? 1 : 0;
+}
+
 extern "C" int nfdpf_cond_stack_backward(const float *params, int n_flows, int dim, int obser_dim,
                                          int hidden, const float *x, const float *cond, int64_t rows,
                                          int inverse, float prior_mean, float prior_std,
@@ -417,10 +431,12 @@ extern "C" int nfdpf_cond_stack_backward(const float *params, int n_flows, int d
   NFDPF_BWD(1, 8)
   NFDPF_BWD(2, 8)
   NFDPF_BWD(16, 8)
+  NFDPF_BWD(8, 8)   // dim 16, 64: the CRNVP measurement's stack at the other built frame-encoding
+  NFDPF_BWD(32, 8)  // widths (meas_widths.hpp; dim = obser_dim = E)
 #undef NFDPF_BWD
   if (!done) {
     set_error("nfdpf_cond_stack_backward: unsupported (dim=%d, hidden=%d); built for dim in "
-              "{2,4,32}, hidden 8",
+              "{2,4,16,32,64}, hidden 8",
               dim, hidden);
     return NFDPF_EINVAL;
   }

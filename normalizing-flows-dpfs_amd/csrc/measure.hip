@@ -1,7 +1,8 @@
 // measure.hip -- standalone measurement models behind nfdpf_measurement:
 // cos (model/models.py:206-219), CRNVP (:256-278), NN (:221-235), gaussian (:237-254).
 // One workgroup per batch row (the row max of CRNVP / gaussian is a row reduction).
-#include "measure.hpp"
+#include "meas_widths.hpp"
+#include "measure_wide.hpp"
 
 namespace nfdpf {
 
@@ -35,7 +36,8 @@ extern "C" int nfdpf_measurement(int kind, const float *pe_params, const float *
                                  int E, float prior_std, float *lik, void *stream) {
   NFDPF_REQUIRE(pe_params && enc && x && lik, "nfdpf_measurement: null pointer");
   NFDPF_REQUIRE(B >= 0 && N >= 1, "nfdpf_measurement: bad sizes");
-  NFDPF_REQUIRE(E == kE, "nfdpf_measurement: built for E = %d (got %d)", kE, E);
+  NFDPF_REQUIRE(meas_width_ok(E), "nfdpf_measurement: frame-encoding width E = %d is not built (%s)", E,
+                kMeasWidthsStr);
   NFDPF_REQUIRE(!(kind == NFDPF_MEAS_CRNVP || kind == NFDPF_MEAS_NN) || meas_params,
                 "nfdpf_measurement: meas_params missing");
   NFDPF_REQUIRE(kind != NFDPF_MEAS_CRNVP || (n_flows >= 0 && prior_std > 0.f),
@@ -43,6 +45,7 @@ extern "C" int nfdpf_measurement(int kind, const float *pe_params, const float *
   if (B == 0) return NFDPF_OK;
   hipStream_t st = as_stream(stream);
   MeasArgs a{pe_params, meas_params, n_flows, prior_std};
+  if (E != kE) return measurement_wide(kind, a, enc, x, B, N, E, lik, st);  // measure_wide.hip
   switch (kind) {
     case NFDPF_MEAS_COS:
       measurement_kernel<256, NFDPF_MEAS_COS><<<B, 256, 0, st>>>(a, enc, x, N, lik);

@@ -156,8 +156,9 @@ class _MeasRunner:
         particle encoder's kernels and the model's own backward; None where a model falls outside
         the kernels (autograd then differentiates ``torch``)."""
         m = self.model
-        if self.kind not in ("cos", "CRNVP", "gaussian", "NN") or enc.dim() != 2 or enc.shape[-1] != 32 or x.dim() != 3 \
-                or x.shape[-1] != 2:
+        from nfdpf._lib import meas_width_supported
+        if self.kind not in ("cos", "CRNVP", "gaussian", "NN") or enc.dim() != 2 or x.dim() != 3 or x.shape[-1] != 2 \
+                or not meas_width_supported(self.kind, enc.shape[-1]):
             return None
         pe = blob(m, "pe", m.particle_encoder, lambda: encoder_tensors(m.particle_encoder), x.device)
         g = gouts[0] if gouts[0] is not None else torch.zeros(x.shape[:2], device=x.device)
@@ -189,7 +190,7 @@ class _MeasRunner:
     def _gaussian_backward(self, pe, enc, x, g):
         """measurement_model_Gaussian (model/models.py:237-254): lik = log N(o - e; mu, s^2 I) minus
         the row max.  The max routes -sum_n g to the row's argmax; dlik/de = (o - e - mu) / s^2
-        (elementwise on the (B, N, 32) encodings); the particle encoder forward and backward are
+        (elementwise on the (B, N, E) encodings); the particle encoder forward and backward are
         the HIP kernels (nfdpf_particle_encoder modes 0 / 1)."""
         dist = self.model.gaussian_distribution
         cov = dist.covariance_matrix
@@ -197,14 +198,15 @@ class _MeasRunner:
         if not torch.equal(cov, torch.eye(cov.shape[0], device=cov.device, dtype=cov.dtype) * var):
             return None  # a non-isotropic covariance: differentiate the PyTorch restatement
         B, N, _ = x.shape
-        es = _ops.particle_encoder_forward(pe, x).view(B, N, 32)
+        E = enc.shape[-1]
+        es = _ops.particle_encoder_forward(pe, x, E).view(B, N, E)
         d = enc[:, None, :] - es - dist.loc.to(es.dtype)
         u = -0.5 * (d * d).sum(-1)  # the log-density up to a constant: only its argmax is used
         am = u.argmax(-1)
         g_u = g.clone()
         g_u[torch.arange(B, device=g.device), am] -= g.sum(-1)
         r = g_u[..., None] * d / var        # = dL/de (lik rises as e approaches o - mu)
-        gx, gp = _ops.particle_encoder_backward(pe, x, r.reshape(B * N, 32).contiguous())
+        gx, gp = _ops.particle_encoder_backward(pe, x, r.reshape(B * N, E).contiguous())
         return -r.sum(1), gx, gp
 
     def _nn_backward(self, pe, enc, x, g):
@@ -215,7 +217,7 @@ class _MeasRunner:
         m = self.model
         B, N, _ = x.shape
         mb = blob(m, "meas", m.likelihood_estimator, lambda: paired_mlp_tensors(m.likelihood_estimator), x.device)
-        es = _ops.particle_encoder_forward(pe, x)
+        es = _ops.particle_encoder_forward(pe, x, enc.shape[-1])
         g_es, g_enc, g_mp = _ops.nn_measurement_backward(mb, enc, es, g)
         gx, gp = _ops.particle_encoder_backward(pe, x, g_es)
         extra, off = [], 0
@@ -233,25 +235,29 @@ class _MeasRunner:
         m = self.model
         fl = list(m.CNF.flows)
         iso = _isotropic(m.CNF.prior)
-        if iso is None or fl[0].dim != 32 or fl[0].hidden_dim != 8 or not 1 <= len(fl) <= 4:
+        E = enc.shape[-1]
+        if iso is None or fl[0].dim != E or fl[0].hidden_dim != 8 or not 1 <= len(fl) <= 4:
             return None
         pm, ps = iso
         B, N, _ = x.shape
         cb = blob(m, "meas", m.CNF.flows, lambda: flows_tensors(m.CNF.flows), x.device)
-        es = _ops.particle_encoder_forward(pe, x)
-        eo = enc[:, None, :].expand(B, N, 32).reshape(B * N, 32).contiguous()
-        _, ld, lp = _ops.cond_stack(cb, len(fl), 32, 32, 8, eo, es, 1, False, pm, ps, want_prior=True)
+        from nfdpf._lib import lib
+        if not lib().nfdpf_cond_stack_backward_supported(len(fl), E, E, 8):
+            return None  # past the stack backward's LDS bound (E = 64 with 4 flows): recompute
+        es = _ops.particle_encoder_forward(pe, x, E)
+        eo = enc[:, None, :].expand(B, N, E).reshape(B * N, E).contiguous()
+        _, ld, lp = _ops.cond_stack(cb, len(fl), E, E, 8, eo, es, 1, False, pm, ps, want_prior=True)
         am = (lp + ld).view(B, N).argmax(-1)
         g_u = g.clone()
         g_u[torch.arange(B, device=g.device), am] -= g.sum(-1)
         g_u = g_u.reshape(-1)
-        g_eo, g_es, g_cb = _ops.cond_stack_backward(cb, len(fl), 32, 32, 8, eo, es, False, torch.zeros_like(eo),
+        g_eo, g_es, g_cb = _ops.cond_stack_backward(cb, len(fl), E, E, 8, eo, es, False, torch.zeros_like(eo),
                                                     g_u, g_u, pm, ps)
         gx, gp = _ops.particle_encoder_backward(pe, x, g_es)
         cnf_params = [p for f in fl for p in f.parameters()]
         gf = blob_grad_to_params(m, "meas", cnf_params, lambda get: flows_tensors(fl, get), g_cb)
         gf = [gi if p.requires_grad else None for gi, p in zip(gf, cnf_params)]
-        return g_eo.view(B, N, 32).sum(1), gx, gp, gf
+        return g_eo.view(B, N, E).sum(1), gx, gp, gf
 
     def torch(self, enc, x):
         return (self.model.torch_forward(enc, x),)

@@ -51,6 +51,7 @@ class FilterDesc(Structure):
         ("meas_mfma", c_int32),
         ("pass_plan", c_void_p),
         ("gate_peers", c_void_p), ("gate_world", c_int32), ("gate_rank", c_int32),
+        ("lik_ext_asis", c_int32),
     ]
 
 
@@ -61,6 +62,7 @@ SIGNATURES = {
     "nfdpf_cond_stack": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int64, c_int64,
                                  c_int, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     "nfdpf_cond_stack_backward_workspace": (c_int64, [c_int, c_int, c_int, c_int, c_int64]),
+    "nfdpf_cond_stack_backward_supported": (c_int, [c_int, c_int, c_int, c_int]),
     "nfdpf_cond_stack_backward": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int64, c_int,
                                           c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                           c_void_p, c_void_p, c_void_p]),
@@ -70,13 +72,18 @@ SIGNATURES = {
     "nfdpf_soft_resample_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                              c_float, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "nfdpf_cos_measurement_backward_workspace": (c_int64, [c_int, c_int]),
+    "nfdpf_cos_measurement_backward_workspace_e": (c_int64, [c_int, c_int, c_int]),
     "nfdpf_cos_measurement_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
                                                c_void_p, c_void_p, c_void_p, c_void_p]),
     "nfdpf_nn_measurement_backward_workspace": (c_int64, [c_int, c_int]),
+    "nfdpf_nn_measurement_backward_workspace_e": (c_int64, [c_int, c_int, c_int]),
     "nfdpf_nn_measurement_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
                                               c_void_p, c_void_p, c_void_p, c_void_p]),
     "nfdpf_particle_encoder": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_void_p]),
+    "nfdpf_particle_encoder_e": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_void_p]),
+    "nfdpf_meas_width_supported": (c_int, [c_int, c_int]),
     "nfdpf_maf_stack": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int64, c_int, c_void_p, c_void_p,
                                 c_void_p]),
     "nfdpf_soft_resample": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int64,
@@ -157,6 +164,28 @@ _lib = None
 
 class NfdpfError(RuntimeError):
     pass
+
+
+_widths = {}
+
+
+def meas_width_supported(kind: str, E: int) -> bool:
+    """Is the measurement ``kind`` ("cos", "CRNVP", "NN", "gaussian") built at frame-encoding width
+    E (--hiddensize)?  The library holds the list (csrc/meas_widths.hpp); this asks it."""
+    return kind in MEAS and bool(lib().nfdpf_meas_width_supported(MEAS[kind], int(E)))
+
+
+def meas_widths(kind: str):
+    """The widths the library is built for (for messages: the list itself lives in the library)."""
+    if kind not in _widths:
+        _widths[kind] = [E for E in range(2, 257) if meas_width_supported(kind, E)]
+    return _widths[kind]
+
+
+def require_meas_width(kind: str, E: int, what: str):
+    if not meas_width_supported(kind, E):
+        raise NfdpfError(f"{what}: the '{kind}' measurement is not built for frame-encoding width {E} "
+                         f"(--hiddensize); supported widths: {', '.join(map(str, meas_widths(kind)))}")
 
 
 def load(path: str = LIB_PATH):

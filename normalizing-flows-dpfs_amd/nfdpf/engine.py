@@ -166,6 +166,7 @@ class FilterEngine:
         # step (as the reference: one host sync per step); otherwise it speculates
         self._ot_fired = False
         self.last_pass_ok = False  # the last run's shapes allow the one-launch pass
+        self._external = cfg.measurement == "CGLOW"  # the measurement runs between the step's two phases
         self.last_pass = False     # the last run's pass ran as one launch (nfdpf_filter_pass_tiled)
         self.pass_launches = 0     # one-launch passes run by this engine (verified or not)
         # a one-launch pass whose row hand-offs timed out (its grid was not all resident: another
@@ -244,7 +245,7 @@ class FilterEngine:
                 self._spec_skip -= 1
             speculate = False
         return bool(speculate and tiled and c.resampler in ("soft", "ot") and not host_mode and not teacher
-                    and not c.force_resample and c.measurement != "CGLOW")
+                    and not c.force_resample and not self._external)
 
     def speculates(self, shard=None, finish=True) -> bool:
         """Whether run() (auto arguments, device RNG) will speculate the gates of its next pass
@@ -375,14 +376,18 @@ class FilterEngine:
         if ok and c.NF_dyn and c.NF_cond and not c.force_resample:
             d.pass_gate, d.B_global = 1, B  # (this rank's rows all resident: sharded, the exchange is per step)
             self._gate_resident = bool(L.lib().nfdpf_filter_pass_supported(ctypes.byref(d)))
-        self.pass_fallback_reason = None if ok else self._shape_limit(B, N)
-        warn = self.pass_fallback_reason and not getattr(self, "_fallback_warned", False)
+        self._note_fallback(None if ok else self._shape_limit(B, N))
+        return ok
+
+    def _note_fallback(self, reason, stacklevel=4):
+        """Record why the one-launch pass does not run (``pass_fallback_reason``) and warn once."""
+        self.pass_fallback_reason = reason
+        warn = reason and not getattr(self, "_fallback_warned", False)
         if warn and os.environ.get("NFDPF_PASS") != "0":
             import warnings
-            warnings.warn(f"nfdpf: the one-launch pass does not cover this shape ({self.pass_fallback_reason}); "
-                          f"running the step launches (about half the speed)", RuntimeWarning, stacklevel=3)
+            warnings.warn(f"nfdpf: the one-launch pass does not cover this shape ({reason}); "
+                          f"running the step launches (about half the speed)", RuntimeWarning, stacklevel=stacklevel)
             self._fallback_warned = True
-        return ok
 
     @staticmethod
     def _shape_limit(B, N):
@@ -498,9 +503,16 @@ class FilterEngine:
         # CGLOW runs as its own kernel between the step's two phases: phase 1 ends with the
         # proposal particles in hist_x slot t, the CGLOW kernel writes their raw likelihood,
         # phase 2 takes it from there (row-max shift, weights, normalisation)
-        external = c.measurement == "CGLOW"
         enc = enc.float().contiguous()
         B, T, E = enc.shape
+        # The other measurements at a built width other than 32 (--hiddensize 16, 64) run the same
+        # way around nfdpf_measurement's width-templated kernel: the step and pass kernels' own
+        # measurement stage is tuned for 32.  cos and NN are not shifted by the reference, so
+        # phase 2 takes their lik_ext as is (d.lik_ext_asis).
+        wide = c.measurement != "CGLOW" and E != 32
+        if wide:
+            L.require_meas_width(c.measurement, E, "FilterEngine.run")
+        external = self._external = c.measurement == "CGLOW" or wide
         N = c.N
         shard = shard or ShardInfo(1, 0, B, 0, None)
         if shard.world == 1 and shard.B_global != B:
@@ -521,6 +533,9 @@ class FilterEngine:
                           and (not c.NF_cond or splittable(self.m.cond_model.flows)))
         pass_ok = (not external and teacher is None and not host_mode
                    and self._pass_supported(B, N, T, E, split_nets, shard))
+        if wide:
+            self._note_fallback(f"frame-encoding width {E}: the one-launch passes are built for --hiddensize 32, "
+                                f"the measurement runs as its own launch between the step's two phases", 3)
         self.last_pass_ok = pass_ok
         xg = self._xgate(shard, pass_ok, finish, dev) if shard.world > 1 else None
         gate_ok = self._gate_ok(shard, pass_ok) and (shard.world == 1 or xg is not None)
@@ -620,6 +635,7 @@ class FilterEngine:
         d.resampler = L.RESAMPLE[c.resampler]
         lik_ext = torch.empty((B, N), **f32) if external else None
         d.lik_ext = L.ptr(lik_ext)
+        d.lik_ext_asis = int(wide and c.measurement in ("cos", "NN"))
         d.rng_mode = L.RNG_HOST if host_mode else L.RNG_DEVICE
         d.force_resample, d.n_flows, d.hidden = int(c.force_resample), c.n_flows, c.hidden
         # tiled + soft: step t's weights are normalised inside step t+1 (one launch fewer per
@@ -632,7 +648,7 @@ class FilterEngine:
         d.seed = int(c.seed) & (2 ** 64 - 1)
         d.dyn_params, d.cond_params = L.ptr(dyn), L.ptr(cond)
         d.pe_params, d.meas_params = L.ptr(pe), L.ptr(meas)
-        if tiled and self._meas_mfma():  # the C3 shape's CRNVP measurement on MFMA (pass and step launches)
+        if tiled and not wide and self._meas_mfma():  # the C3 shape's CRNVP measurement on MFMA (pass and step launches)
             mf = self._mfma_blob(dev)
             d.meas_params, d.meas_mfma = mf.data_ptr(), 1  # (caching-allocator blocks: 512-B aligned)
         d.enc, d.lin = enc.data_ptr(), L.ptr(lin)
@@ -823,8 +839,13 @@ class FilterEngine:
                 d.phase = 1
                 step()
                 if ev is not None:
-                    ev.record_start(dev)  # the CGLOW kernel is the step's dominant launch
-                ops.cglow_measurement(pe, meas, enc[:, t], hx[:, t], K=self.m.cglow_measurement.flow.K, out=lik_ext)
+                    ev.record_start(dev)  # the measurement kernel is the step's dominant launch
+                if wide:
+                    ops.measurement(c.measurement, pe, meas, c.n_flows, enc[:, t], hx[:, t], c.meas_prior_std,
+                                    out=lik_ext)
+                else:
+                    ops.cglow_measurement(pe, meas, enc[:, t], hx[:, t], K=self.m.cglow_measurement.flow.K,
+                                          out=lik_ext)
                 if ev is not None:
                     ev.record_end(dev)
                 d.phase = 2

@@ -181,17 +181,29 @@ def soft_resample_backward(p, idx, w_out, g_x_out, g_w_out, alpha, D, row_base=0
     return gx, gp
 
 
+def encoder_param_count(E: int) -> int:
+    """Parameters of the particle encoder Linear(2,16) Linear(16,32) Linear(32,E) (1648 at E = 32)."""
+    return 2 * 16 + 16 + 16 * 32 + 32 + 32 * E + E
+
+
+def nn_head_param_count(E: int) -> int:
+    """Parameters of likelihood_est Linear(2E,64) Linear(64,64) Linear(64,1) (8385 at E = 32)."""
+    return 64 * 2 * E + 64 + 64 * 64 + 64 + 64 + 1
+
+
 def cos_measurement_backward(pe_blob, enc, x, g_lik):
-    """Backward of the cosine measurement -> (g_enc [B, E], g_x [B, N, 2], g_params [1648] in
-    nn.Linear order W1 b1 W2 b2 W3 b3) (include/nfdpf.h nfdpf_cos_measurement_backward)."""
+    """Backward of the cosine measurement -> (g_enc [B, E], g_x [B, N, 2], g_params
+    [encoder_param_count(E)] in nn.Linear order W1 b1 W2 b2 W3 b3) (include/nfdpf.h
+    nfdpf_cos_measurement_backward)."""
     require_device(x, "cos_measurement_backward")
     B, N, _ = x.shape
     enc, x, g_lik = _c(enc), _c(x), _c(g_lik)
     E = enc.shape[-1]
+    L.require_meas_width("cos", E, "cos_measurement_backward")
     g_enc = torch.empty_like(enc)
     gx = torch.empty_like(x)
-    gp = torch.empty(1648, device=x.device, dtype=f32)
-    nb = int(lib().nfdpf_cos_measurement_backward_workspace(B, N))
+    gp = torch.empty(encoder_param_count(E), device=x.device, dtype=f32)
+    nb = int(lib().nfdpf_cos_measurement_backward_workspace_e(B, N, E))
     ws = torch.empty(max(1, nb // 4), device=x.device, dtype=f32)
     check(lib().nfdpf_cos_measurement_backward(ptr(pe_blob), ptr(enc), ptr(x), ptr(g_lik), B, N, E, ptr(g_enc),
                                                ptr(gx), ptr(gp), ptr(ws), stream_ptr(x.device)),
@@ -199,41 +211,48 @@ def cos_measurement_backward(pe_blob, enc, x, g_lik):
     return g_enc, gx, gp
 
 
-def particle_encoder_forward(pe_blob, x):
-    """PE(x) -> [B*N, 32] (nfdpf_particle_encoder mode 0)."""
+def particle_encoder_forward(pe_blob, x, E=32):
+    """PE(x) -> [B*N, E] (nfdpf_particle_encoder_e mode 0)."""
     require_device(x, "particle_encoder_forward")
+    L.require_meas_width("cos", E, "particle_encoder_forward")
     B, N, _ = x.shape
     x = _c(x)
-    e = torch.empty((B * N, 32), device=x.device, dtype=f32)
-    check(lib().nfdpf_particle_encoder(0, ptr(pe_blob), ptr(x), B, N, None, ptr(e), None, None, None,
-                                       stream_ptr(x.device)), "nfdpf_particle_encoder")
+    e = torch.empty((B * N, E), device=x.device, dtype=f32)
+    check(lib().nfdpf_particle_encoder_e(0, ptr(pe_blob), ptr(x), B, N, int(E), None, ptr(e), None, None, None,
+                                         stream_ptr(x.device)), "nfdpf_particle_encoder")
     return e
 
 
 def particle_encoder_backward(pe_blob, x, g_e):
-    """-> (g_x [B, N, 2], g_params [1648] nn.Linear order) (nfdpf_particle_encoder mode 1)."""
+    """g_e [B*N, E] -> (g_x [B, N, 2], g_params [encoder_param_count(E)] nn.Linear order)
+    (nfdpf_particle_encoder_e mode 1)."""
     require_device(x, "particle_encoder_backward")
     B, N, _ = x.shape
     x, g_e = _c(x), _c(g_e)
+    E = g_e.shape[-1]
+    L.require_meas_width("cos", E, "particle_encoder_backward")
     gx = torch.empty_like(x)
-    gp = torch.empty(1648, device=x.device, dtype=f32)
-    nb = int(lib().nfdpf_cos_measurement_backward_workspace(B, N))
+    gp = torch.empty(encoder_param_count(E), device=x.device, dtype=f32)
+    nb = int(lib().nfdpf_cos_measurement_backward_workspace_e(B, N, E))
     ws = torch.empty(max(1, nb // 4), device=x.device, dtype=f32)
-    check(lib().nfdpf_particle_encoder(1, ptr(pe_blob), ptr(x), B, N, ptr(g_e), None, ptr(gx), ptr(gp), ptr(ws),
-                                       stream_ptr(x.device)), "nfdpf_particle_encoder")
+    check(lib().nfdpf_particle_encoder_e(1, ptr(pe_blob), ptr(x), B, N, int(E), ptr(g_e), None, ptr(gx), ptr(gp),
+                                         ptr(ws), stream_ptr(x.device)), "nfdpf_particle_encoder")
     return gx, gp
 
 
 def nn_measurement_backward(meas_blob, enc, es, g_lik):
-    """Backward of the NN likelihood head -> (g_e [B*N, 32], g_enc [B, 32], g_params [8385] in
-    nn.Linear order) for encodings es = PE(x) [B*N, 32] (nfdpf_nn_measurement_backward)."""
+    """Backward of the NN likelihood head -> (g_e [B*N, E], g_enc [B, E], g_params
+    [nn_head_param_count(E)] in nn.Linear order) for encodings es = PE(x) [B*N, E]
+    (nfdpf_nn_measurement_backward)."""
     require_device(es, "nn_measurement_backward")
     B, N = g_lik.shape
     enc, es, g_lik = _c(enc), _c(es), _c(g_lik)
+    E = enc.shape[-1]
+    L.require_meas_width("NN", E, "nn_measurement_backward")
     g_e = torch.empty_like(es)
     g_enc = torch.empty_like(enc)
-    gp = torch.empty(8385, device=es.device, dtype=f32)
-    nb = int(lib().nfdpf_nn_measurement_backward_workspace(B, N))
+    gp = torch.empty(nn_head_param_count(E), device=es.device, dtype=f32)
+    nb = int(lib().nfdpf_nn_measurement_backward_workspace_e(B, N, E))
     ws = torch.empty(max(1, nb // 4), device=es.device, dtype=f32)
     check(lib().nfdpf_nn_measurement_backward(ptr(meas_blob), ptr(enc), ptr(es), ptr(g_lik), B, N, enc.shape[-1],
                                               ptr(g_e), ptr(g_enc), ptr(gp), ptr(ws), stream_ptr(es.device)),
@@ -400,12 +419,16 @@ def normalize_log_probs(logw, add=0.0):
     return p, ie
 
 
-def measurement(kind: str, pe_blob, meas_blob, n_flows, enc, x, prior_std=2.5):
-    """measurement models (model/models.py:206-278) -> lik [B,N]."""
+def measurement(kind: str, pe_blob, meas_blob, n_flows, enc, x, prior_std=2.5, out=None):
+    """measurement models (model/models.py:206-278) -> lik [B,N] (``out``: a contiguous float32
+    [B, N] buffer to write instead of a new one).  enc [B, E] at a width the library is built for
+    (nfdpf._lib.meas_widths)."""
     require_device(x, "measurement")
     enc, x = _c(enc), _c(x)
     B, N, _ = x.shape
-    lik = torch.empty((B, N), device=x.device, dtype=f32)
+    if out is not None and (out.dtype != f32 or tuple(out.shape) != (B, N) or not out.is_contiguous()):
+        raise L.NfdpfError("measurement: out must be a contiguous float32 [B, N] tensor")
+    lik = out if out is not None else torch.empty((B, N), device=x.device, dtype=f32)
     check(lib().nfdpf_measurement(L.MEAS[kind], ptr(pe_blob), ptr(meas_blob), int(n_flows), ptr(enc), ptr(x),
                                   B, N, enc.shape[-1], float(prior_std), ptr(lik), stream_ptr(x.device)),
           "nfdpf_measurement")
