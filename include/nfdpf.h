@@ -498,11 +498,9 @@ NFDPF_API int nfdpf_filter_step(const nfdpf_filter_desc *d, void *stream);
  * the T steps of one sequence.                                                        */
 NFDPF_API int64_t nfdpf_filter_tiled_workspace_bytes(int B, int N, int T);
 NFDPF_API int nfdpf_filter_tiled_tiles(int N);
-/* 1 when nfdpf_filter_step_tiled runs this step as ONE launch (tiled_step_fused_kernel: the
- * C2-shaped path -- split RealNVP nets, NF_cond, cosine measurement -- with every workgroup of
- * the (tiles, B) grid resident on the current device; opt-in: NFDPF_FUSED_STEP=1), else 0.
- * prof_front is then ignored (no separate front launch).  No reference counterpart: a query. */
-NFDPF_API int nfdpf_filter_tiled_fused(const nfdpf_filter_desc *d);
+/* (The step as ONE launch on the C2-shaped path, opt-in and queried through
+ * nfdpf_filter_tiled_fused, measured 1.483 vs 1.471 ms per pass against the two launches.  The
+ * code was retired with its query; f81620f is the last commit that holds it.) */
 /* sizeof(nfdpf_filter_desc) as this library was built: a binding checks its mirror of the
  * struct against it (nfdpf._lib does, at load).  No reference counterpart: a query. */
 NFDPF_API int64_t nfdpf_filter_desc_size(void);

@@ -29,10 +29,6 @@
 
 namespace nfdpf {
 namespace cg {
-#ifdef NFDPF_EXP_CGDUMP
-__device__ float g_cgdump[256];
-#endif
-
 constexpr int kTileP = 16;    // particles per workgroup tile
 constexpr int kThreads = 256;
 
@@ -48,9 +44,6 @@ struct Lds {
   float an[kTileP][2 * kC + 1];        // actnorm (logs | bias)
   float wm[kTileP][kC * kC + 4];       // 1x1 conv weight, row-major [out][in] (rows 16-B aligned)
   float ld[kTileP];                    // per-particle log-det of actnorm + 1x1 conv
-#ifdef NFDPF_EXP_CGDUMP
-  float ldw_dbg[kTileP];
-#endif
   int row[kTileP];
   float escale[2 * kYH + kC];          // exp of the coupling net's log-scales (once per launch)
   float zrow[kC + 1];                  // zeros: the 3x3 convolutions' out-of-grid neighbour
@@ -76,15 +69,6 @@ struct Lds {
 typedef float f4 __attribute__((ext_vector_type(4)));
 
 __shared__ Lds S;  // one instance per workgroup, shared by the phase functions below
-
-#ifdef NFDPF_EXP_CGTRACE  // experiment: per-phase timestamps of one tile per workgroup
-__device__ uint64_t g_cgtrace[1024][16];
-#define CGTRACE(k)                                                                  \
-  if (trace_it && threadIdx.x == 0 && blockIdx.x < 1024)                           \
-    g_cgtrace[blockIdx.x][k] = __builtin_amdgcn_s_memrealtime();
-#else
-#define CGTRACE(k)
-#endif
 
 // One 16x16 output tile of C = A B over K (zero-padded to 4*KSTEPS): lane l feeds A[l&15][k]
 // and B[k][l&15] for k = 4s + (l>>4), and gets C rows 4(l>>4)+i, column l&15.
@@ -115,16 +99,10 @@ __device__ __forceinline__ void mfma_store(const f4 &acc, const FE &epi) {
 __device__ __forceinline__ float sigmoidf_(float v) { return 1.0f / (1.0f + expf(-v)); }
 
 // tanh of the conditioning nets' outputs and of the coupling's shift / scale: libm tanhf.
-// (-DNFDPF_CG_FAST_TANH: tanh_fast, common.hpp -- 2 % faster per launch, but the golden
-// error grows from 1.8e-6 to 5.5e-6 against the reference's own 2.1e-6: not shipped.  Round 3:
-// libm's two regimes evaluated branch-free and selected, ~2 ulp -- 2.03 ms either way, removed.)
-__device__ __forceinline__ float cg_tanh(float x) {
-#if defined(NFDPF_CG_FAST_TANH)
-  return tanh_fast(x);
-#else
-  return tanhf(x);
-#endif
-}
+// (tanh_fast, common.hpp, was 2 % faster per launch, but the golden error grew from 1.8e-6 to
+// 5.5e-6 against the reference's own 2.1e-6: not shipped.  Round 3: libm's two regimes
+// evaluated branch-free and selected, ~2 ulp -- 2.03 ms either way, removed.)
+__device__ __forceinline__ float cg_tanh(float x) { return tanhf(x); }
 
 // A lane-dependent weight load through a GLOBAL pointer (a generic one compiles to flat_load,
 // which also counts on lgkmcnt: every LDS wait would then wait for it too), unconditional --
@@ -146,40 +124,6 @@ __device__ __forceinline__ const float *sgpr_ptr(const float *p) {
 // pivoting by |value|; every lane of the group returns the same value.  The pivot search is a
 // 16-lane (|v|, lane) max on DPP (ties to the lowest lane); the pivot row goes through LDS
 // (the pivot lane writes it to prow_lds, the group reads it back: same wave, in order).
-#ifdef NFDPF_CG_SHFL_LU
-__device__ float logabsdet12(float (&a)[kC], int q, float *) {
-  const int base = (threadIdx.x & 63) & ~15;  // first lane of this particle's group
-  float ld = 0.f;
-  bool done = q >= kC;                        // lanes 12..15 hold no row
-#pragma unroll
-  for (int k = 0; k < kC; ++k) {
-    float v = done ? -1.f : fabsf(a[k]);
-    int who = q;
-#pragma unroll
-    for (int o = 8; o > 0; o >>= 1) {
-      const float v2 = __shfl_xor(v, o, 16);
-      const int w2 = __shfl_xor(who, o, 16);
-      if (v2 > v || (v2 == v && w2 < who)) {
-        v = v2;
-        who = w2;
-      }
-    }
-    float prow[kC];
-#pragma unroll
-    for (int j = 0; j < kC; ++j) prow[j] = __shfl(a[j], base + who, 64);
-    const float piv = prow[k];
-    ld += logf(fabsf(piv));
-    if (q == who) done = true;
-    if (!done) {
-      const float f = a[k] / piv;
-#pragma unroll
-      for (int j = 0; j < kC; ++j)
-        if (j > k) a[j] = fmaf(-f, prow[j], a[j]);
-    }
-  }
-  return ld;
-}
-#elif !defined(NFDPF_CG_EXACT_LU)
 // The pivot search as ONE unsigned max per DPP step: the key of a lane is |a[k]|'s bit pattern
 // (monotonic in the value for non-negative floats) with its low 4 mantissa bits replaced by
 // 15 - lane, so the 16-lane max picks the largest |value| -- to 2^-19 relative; among values
@@ -187,7 +131,8 @@ __device__ float logabsdet12(float (&a)[kC], int q, float *) {
 // pivot already (and lanes 12..15) hold key 0 and never win: a live lane's key is >= 4.  The
 // multiplier is a[k] times the pivot's reciprocal (v_rcp_f32, 1 ulp).  Round 2's search (an
 // exact compare-and-select argmax, branchy after compilation: ~70 instructions per pivot) and
-// IEEE division (11) stay behind -DNFDPF_CG_EXACT_LU.
+// IEEE division (11), and a __shfl version of the search, are retired: f81620f is the last
+// commit that holds them.
 template <int CTRL>
 __device__ __forceinline__ uint32_t dpp_max_u(uint32_t v) {
   return max(v, (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, CTRL, 0xf, 0xf, false));
@@ -225,59 +170,13 @@ __device__ __forceinline__ float logabsdet12(float (&a)[kC], int q, float *prow_
   }
   return ld;
 }
-#else
-template <int CTRL>
-__device__ __forceinline__ void argmax_step(float &v, int &who) {
-  const float v2 = dpp_f<CTRL>(v);
-  const int w2 = __builtin_amdgcn_update_dpp(who, who, CTRL, 0xf, 0xf, false);
-  if (v2 > v || (v2 == v && w2 < who)) {
-    v = v2;
-    who = w2;
-  }
-}
-__device__ __forceinline__ float logabsdet12(float (&a)[kC], int q, float *prow_lds) {
-  float ld = 0.f;
-  bool done = q >= kC;  // lanes 12..15 hold no row
-#pragma unroll
-  for (int k = 0; k < kC; ++k) {
-    float v = done ? -1.f : fabsf(a[k]);
-    int who = q;
-    argmax_step<kDppXor1>(v, who);
-    argmax_step<kDppXor2>(v, who);
-    argmax_step<kDppHalfMirror>(v, who);
-    argmax_step<kDppMirror>(v, who);
-    if (q == who)
-#pragma unroll
-      for (int j = k; j < kC; ++j) prow_lds[j] = a[j];
-    __builtin_amdgcn_wave_barrier();
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    float prow[kC];
-#pragma unroll
-    for (int j = k; j < kC; ++j) prow[j] = prow_lds[j];
-    const float piv = prow[k];
-    ld += logf(fabsf(piv));
-    if (q == who) done = true;
-    if (!done) {
-      const float f = a[k] / piv;
-#pragma unroll
-      for (int j = k + 1; j < kC; ++j) a[j] = fmaf(-f, prow[j], a[j]);
-    }
-    __builtin_amdgcn_wave_barrier();  // every lane has read the row before the next is written
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  }
-  return ld;
-}
-#endif
 
 }  // namespace cg
 
 using namespace cg;
 
-// phase_resize / phase_f as calls (default) or inlined (-DNFDPF_CG_PHASE_INLINE=__forceinline__:
-// 156 B of scratch, not run)
-#ifndef NFDPF_CG_PHASE_INLINE
-#define NFDPF_CG_PHASE_INLINE __noinline__
-#endif
+// phase_resize / phase_f are calls (__noinline__): inlined (__forceinline__) the kernel took
+// 156 B of scratch (not run)
 
 // workgroup barrier that is also a scheduling fence
 #define SYNC()                            \
@@ -289,11 +188,7 @@ using namespace cg;
 // From phase_y to the tile's end every LDS hand-off stays inside one particle's 16 lanes (lane
 // = (particle tid / 16, position tid % 16): the 3x3 neighbourhoods, S.yv, S.ex, S.ld), i.e.
 // inside one wave, whose LDS accesses execute in order: a compiler fence suffices, and the
-// waves run those phases without waiting for each other.  (-DNFDPF_CG_BARRIERS: workgroup
-// barriers there, as in r01.)
-#ifdef NFDPF_CG_BARRIERS
-#define WSYNC() SYNC()
-#else
+// waves run those phases without waiting for each other.  (r01 had workgroup barriers there.)
 #define WSYNC()                                          \
   do {                                                   \
     __builtin_amdgcn_sched_barrier(0);                   \
@@ -301,7 +196,6 @@ using namespace cg;
     __builtin_amdgcn_wave_barrier();                     \
     __builtin_amdgcn_sched_barrier(0);                   \
   } while (0)
-#endif
 
 // squeeze(y) at position q (y prefetched at the tile's start: yq = y_fetch(...)),
 // cond-actnorm, cond-1x1 conv (-> S.yv), their log-dets (-> S.ld)
@@ -345,16 +239,13 @@ __device__ __forceinline__ void phase_y(float (&y)[kC], int p, int q) {
   // the pivot rows go through this particle's S.ex[p][0] (free until phase_resize writes it)
   const float ldw = logabsdet12(wr, q, &S.ex[p][0][0]);
   if (q == 0) S.ld[p] = 16.0f * sl + 16.0f * ldw;  // dimensions (4x4) x (sum logs, log|det W|)
-#ifdef NFDPF_EXP_CGDUMP
-  if (q == 0) S.ldw_dbg[p] = ldw;
-#endif
 }
 
 // resize_x = conv3x3(3->16, pad 1) ReLU, conv2x2/2(16->6) ReLU, fused per 4x4 position (the
 // 2x2 block of 8x8 conv1 outputs stays in registers) -> S.ex[p][q][0:6].  Weights are stored
 // tap-major, output channel fastest (nfdpf.pack.cglow_tensors), so each input value feeds a
 // contiguous run of output-channel pairs (v_pk_fma_f32 with an SGPR pair).
-__device__ NFDPF_CG_PHASE_INLINE void phase_resize(const float *glow_, int p, int q) {
+__device__ __noinline__ void phase_resize(const float *glow_, int p, int q) {
   const float *glow = sgpr_ptr(glow_);
   const int qi = q >> 2, qj = q & 3;
   // The 4x4 window (rows 2qi-1 .. 2qi+2, cols 2qj-1 .. 2qj+2, zero outside) is read from LDS per
@@ -375,10 +266,8 @@ __device__ NFDPF_CG_PHASE_INLINE void phase_resize(const float *glow_, int p, in
   }
 // tap loop unrolled by 9 (one (dr) row of taps: its weight loads issue ahead of the fmas):
 // 2.33 -> 2.28 ms per C5 launch against unroll 3; unroll 1 2.43 ms; 27 spills to scratch
-#ifndef NFDPF_CG_RESIZE_UNROLL
-#define NFDPF_CG_RESIZE_UNROLL 9
-#endif
-#pragma unroll NFDPF_CG_RESIZE_UNROLL
+  constexpr int kResizeUnroll = 9;
+#pragma unroll kResizeUnroll
   for (int t = 0; t < 27; ++t) {  // taps (dr, ds, c) of the 3x3x3 window
     F2 = (cf2 *)wptr(glow + kOffF);
     const int dr = t / 9, ds = (t / 3) % 3, c = t % 3;
@@ -429,25 +318,10 @@ __device__ NFDPF_CG_PHASE_INLINE void phase_resize(const float *glow_, int p, in
 template <int CIN, int NP>
 __device__ __forceinline__ void conv3x3(const float *glow, int wofs, int p, int q, f2 (&acc)[NP]) {
   const int qi = q >> 2, qj = q & 3;
-#ifdef NFDPF_CG_CONV_TC
-#pragma unroll 2
-  for (int tc = 0; tc < 9 * CIN; ++tc) {  // (tap, input channel), tap-major
-    const int t9 = tc / CIN, c = tc - CIN * (tc / CIN);
-    const int dr = t9 / 3, ds = t9 - 3 * (t9 / 3);
-    cf2 *F2 = (cf2 *)wptr(glow + kOffF);  // a few weights live at a time
-    const int rr = qi + dr - 1, ss = qj + ds - 1;
-    const bool in = rr >= 0 && rr < 4 && ss >= 0 && ss < 4;
-    const float v = in ? S.ex[p][rr * 4 + ss][c] : 0.f;
-#pragma unroll
-    for (int n = 0; n < NP; ++n) acc[n] = pfma(F2[(wofs + tc * (2 * NP)) / 2 + n], splat(v), acc[n]);
-  }
-#else
   constexpr int kChunk = CIN % 4 == 0 ? 4 : (CIN % 3 == 0 ? 3 : 2);
 // (unrolled by 3: 2.71 vs 2.33 ms per C5 launch, 32 B of scratch; by 9: 724 B of scratch)
-#ifndef NFDPF_CG_CONV_UNROLL
-#define NFDPF_CG_CONV_UNROLL 1
-#endif
-#pragma unroll NFDPF_CG_CONV_UNROLL
+  constexpr int kConvUnroll = 1;
+#pragma unroll kConvUnroll
   for (int t9 = 0; t9 < 9; ++t9) {
     const int dr = t9 / 3, ds = t9 - 3 * (t9 / 3);
     const int rr = qi + dr - 1, ss = qj + ds - 1;
@@ -469,7 +343,6 @@ __device__ __forceinline__ void conv3x3(const float *glow, int wofs, int p, int 
           acc[n] = pfma(F2[(wofs + (t9 * CIN + c) * (2 * NP)) / 2 + n], splat(v[c]), acc[n]);
     }
   }
-#endif
 }
 
 // resize conv3, the coupling net f, the affine update of z2 and the Gaussian log-prob;
@@ -478,7 +351,7 @@ __device__ __forceinline__ void conv3x3(const float *glow, int wofs, int p, int 
 // alone.  KEEP: z2 goes back to S.yv next to z1, so the caller finds this step's output
 // (12 channels at this lane's position) there: the next step's input.
 template <bool TOP, bool KEEP>
-static __device__ NFDPF_CG_PHASE_INLINE float phase_f(const float *glow_, int p, int q, float *zrow) {
+static __device__ __noinline__ float phase_f(const float *glow_, int p, int q, float *zrow) {
   const float *glow = sgpr_ptr(glow_);
   cfloat *F = wptr(glow + kOffF);
   float fin[kC];  // cat(resize_x(x), z1)
@@ -570,15 +443,13 @@ static __device__ NFDPF_CG_PHASE_INLINE float phase_f(const float *glow_, int p,
 // 3 workgroups per CU: 50 KB of LDS each (the stage union of Lds) and <= 168 VGPRs (162) for
 // 3 waves per SIMD.  (r01f: min-blocks 2 with 80 KB of LDS spilled 182 SGPRs and ran 5.24 ms
 // at C5; min-blocks 1, same occupancy, 5.09 ms; the union + min-blocks 3 4.72 ms -- A/B, 3 runs.)
-#ifndef NFDPF_CG_WGS
-#define NFDPF_CG_WGS 3  // resident workgroups per CU (LDS 50 KB, <= 168 VGPRs); 2: 2.52 vs 2.12 ms
-#endif
+constexpr int kCgWgs = 3;  // resident workgroups per CU (LDS 50 KB, <= 168 VGPRs); 2: 2.52 vs 2.12 ms
 // MULTI: `nsteps` CondGlowSteps per tile (step k's parameters at glow + k * kStep), step k > 0
 // reading step k-1's output from registers; !MULTI is the K = 1 kernel (nsteps unused).
 // MID (with MULTI): the backward's forward pass -- every step's output z_k goes to
 // zout + (k * total + particle) * 192, no Gaussian term, no lik.
 template <bool MULTI, bool MID>
-__global__ __launch_bounds__(kThreads, NFDPF_CG_WGS) void cglow_kernel(const float *__restrict__ pe,
+__global__ __launch_bounds__(kThreads, kCgWgs) void cglow_kernel(const float *__restrict__ pe,
                                                             const float *__restrict__ glow,
                                                             const float *__restrict__ enc,
                                                             int64_t enc_rs, const float *__restrict__ x,
@@ -603,10 +474,6 @@ __global__ __launch_bounds__(kThreads, NFDPF_CG_WGS) void cglow_kernel(const flo
   }
 
   for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-#ifdef NFDPF_EXP_CGTRACE
-    const bool trace_it = tile == blockIdx.x + 2 * (int64_t)gridDim.x;
-#endif
-    CGTRACE(0)
     // this lane's squeezed y (phase_y), fetched now so its latency hides behind the encoder
     // and the conditioning nets (lane = (particle w * 4 + l / 16, position l % 16))
     float yq[kC];
@@ -681,7 +548,6 @@ __global__ __launch_bounds__(kThreads, NFDPF_CG_WGS) void cglow_kernel(const flo
       }
       SYNC();
     }
-    CGTRACE(1)
     const int ksteps = MULTI ? nsteps : 1;
     float ldacc = 0.f;  // MULTI: the steps' log-dets so far
     // (a do-while whose back edge is compile-time false without MULTI: the K = 1 kernel has
@@ -738,7 +604,6 @@ __global__ __launch_bounds__(kThreads, NFDPF_CG_WGS) void cglow_kernel(const flo
       }
     }
     SYNC();
-    CGTRACE(2)
     float bC3[8], bbC3, bL0[2], bbL0, bL2[4], bbL2;  // cond conv3, x_Linear of net w (w < 2)
     {
       const float *G = w ? gI : gA;
@@ -773,7 +638,6 @@ __global__ __launch_bounds__(kThreads, NFDPF_CG_WGS) void cglow_kernel(const flo
       });
     }
     SYNC();
-    CGTRACE(3)
     float bL4[3][4], bbL4[3];  // last layer: jobs w, w + 4, w + 8 (< 11)
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
@@ -799,7 +663,6 @@ __global__ __launch_bounds__(kThreads, NFDPF_CG_WGS) void cglow_kernel(const flo
       });
     }
     SYNC();
-    CGTRACE(4)
     // x_Linear: 8 -> 16 -> 16 (ReLU)
     if (w < 2) {
       const int net = w;
@@ -813,7 +676,6 @@ __global__ __launch_bounds__(kThreads, NFDPF_CG_WGS) void cglow_kernel(const flo
       mfma_store(acc, [&](int r, int c, float v) { S.v1[r][net * kXS + c] = relu(v + bbL2); });
     }
     SYNC();
-    CGTRACE(5)
     // last layer + tanh: actnorm (24 = 2 tiles) and 1x1 conv (144 = 9 tiles)
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
@@ -834,15 +696,12 @@ __global__ __launch_bounds__(kThreads, NFDPF_CG_WGS) void cglow_kernel(const flo
       });
     }
     SYNC();
-    CGTRACE(6)
 
     // ---- squeeze(y) at position q, cond-actnorm, cond-1x1 conv, log|det W|
     phase_y(yq, p, q);
     WSYNC();
-    CGTRACE(7)
     phase_resize(gs, p, q);
     WSYNC();
-    CGTRACE(8)
     const int64_t gi = g0 + p;
     if (MULTI && (MID || k + 1 < ksteps)) {
       // not the last step: its output (left in S.yv) is the next step's input, carried in
@@ -857,18 +716,6 @@ __global__ __launch_bounds__(kThreads, NFDPF_CG_WGS) void cglow_kernel(const flo
     // the last step
     if (MULTI) ldacc += S.ld[p];
     const float part = phase_f<true, false>(gs, p, q, zout && gi < total ? zout + gi * kE : nullptr);
-#ifdef NFDPF_EXP_CGDUMP
-    // experiment only: one particle's 1x1-conv W, its log|det W| (the LU's), actnorm outputs
-    if (gi == (int64_t)NFDPF_CG_TARGET && q < 16) {
-      for (int k = q; k < kC * kC; k += 16) g_cgdump[k] = S.wm[p][k];
-      for (int k = q; k < 2 * kC; k += 16) g_cgdump[160 + k] = S.an[p][k];
-      if (q == 0) {
-        g_cgdump[200] = S.ldw_dbg[p];
-        g_cgdump[201] = S.ld[p];
-        g_cgdump[202] = part;
-      }
-    }
-#endif
     if (!MID && q == 0 && gi < total) {
       // logdet0 = -log(256) * 192, plus actnorm / 1x1-conv log-dets, plus this particle's sum
       const float obj = (-5.545177444479562f * (float)kE + (MULTI ? ldacc : S.ld[p])) + part;
@@ -878,24 +725,12 @@ __global__ __launch_bounds__(kThreads, NFDPF_CG_WGS) void cglow_kernel(const flo
     }
     } while (MULTI && ++k < ksteps);
     SYNC();
-    CGTRACE(9)
   }
 }
 
 }  // namespace nfdpf
 
 using namespace nfdpf;
-
-#ifdef NFDPF_EXP_CGDUMP
-extern "C" NFDPF_API int nfdpf_exp_cgdump_read(void *host) {
-  return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_cgdump), sizeof(g_cgdump)) == hipSuccess ? 0 : 1;
-}
-#endif
-#ifdef NFDPF_EXP_CGTRACE
-extern "C" NFDPF_API int nfdpf_exp_cgtrace_read(void *host) {
-  return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_cgtrace), sizeof(g_cgtrace)) == hipSuccess ? 0 : 1;
-}
-#endif
 
 extern "C" int64_t nfdpf_cglow_params_size(int K) { return K >= 1 && K <= kMaxK ? (int64_t)K * kStep : -1; }
 
@@ -914,7 +749,7 @@ extern "C" int nfdpf_cglow_measurement(const float *pe_params, const float *glow
   }
   // a persistent grid of exactly the resident workgroups (3 per CU: LDS 50 KB, 162 VGPRs):
   // more would start a second, late round of workgroups and leave the tail unbalanced
-  const int grid = (int)std::min<int64_t>(tiles, (int64_t)cus * NFDPF_CG_WGS);
+  const int grid = (int)std::min<int64_t>(tiles, (int64_t)cus * kCgWgs);
   if (K == 1)
     cglow_kernel<false, false><<<grid, kThreads, 0, as_stream(stream)>>>(
         pe_params, glow_params, enc, enc_rs, x, x_rs, B, N, lik, lik_rs, nullptr, nullptr, 1.0f, 1);
@@ -930,7 +765,7 @@ static int cglow_grid(int64_t tiles) {
     int v = 0;
     if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
   }
-  return (int)std::min<int64_t>(tiles, (int64_t)cus * NFDPF_CG_WGS);
+  return (int)std::min<int64_t>(tiles, (int64_t)cus * kCgWgs);
 }
 
 extern "C" int nfdpf_cglow_flow(const float *glow_params, int K, const float *x, const float *y, int64_t M,

@@ -196,18 +196,6 @@ struct BLds {
 };
 static_assert(sizeof(BLds) <= 160 * 1024, "cglow_bwd: LDS above 160 KB");
 
-#ifdef NFDPF_EXP_CBTRACE  // experiment: per-phase timestamps of one tile per workgroup
-__device__ uint64_t g_cbtrace[256][24];
-#define CBT(k)                                                                        \
-  do {                                                                                \
-    if (cbt_on && threadIdx.x == 0) g_cbtrace[blockIdx.x & 255][k] = __builtin_amdgcn_s_memrealtime(); \
-  } while (0)
-#else
-#define CBT(k) \
-  do {         \
-  } while (0)
-#endif
-
 template <int CTRL>
 __device__ __forceinline__ uint32_t dpp_max_u(uint32_t v) {
   return max(v, (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, CTRL, 0xf, 0xf, false));
@@ -288,14 +276,10 @@ __global__ __launch_bounds__(kThreads, 1) void cglow_bwd_kernel(
     const float *gw_ = glow, *pe = pe_;
     asm volatile("" : "+s"(gw_), "+s"(pe));
     const float *gA = gw_ + kOffA, *gI = gw_ + kOffI, *F = gw_ + kOffF;
-#ifdef NFDPF_EXP_CBTRACE
-    const bool cbt_on = tile == blockIdx.x + 2 * (int64_t)gridDim.x;
-#endif
     const int64_t m_raw = tile * kTP + p;
     const bool valid = m_raw < M;
     const int64_t m = valid ? m_raw : M - 1;  // invalid lanes recompute a real particle, upstream 0
     const int rowb = PART ? (int)(m / N) : (int)m;
-    CBT(0);
     // ---------------- forward recompute ----------------
     float yq[kC];  // squeezed y at position q: channel c * 4 + f
     {
@@ -354,7 +338,6 @@ __global__ __launch_bounds__(kThreads, 1) void cglow_bwd_kernel(
       for (int k = 0; k < kE / 16; ++k) S.X[p][q + 16 * k] = x[m * kE + q + 16 * k];
     }
     __syncthreads();
-    CBT(1);
     // conditioning nets: conv1 (3 -> 8, 2x2 stride 2, 8x8 -> 4x4) at position q
     {
       float in[12];
@@ -437,7 +420,6 @@ __global__ __launch_bounds__(kThreads, 1) void cglow_bwd_kernel(
         S.an[p][n] = t;
     }
     __syncthreads();
-    CBT(2);
     // actnorm, 1x1 conv at position q
     float yw[kC];
     {
@@ -460,7 +442,6 @@ __global__ __launch_bounds__(kThreads, 1) void cglow_bwd_kernel(
         yw[o] = a;
       }
     }
-    CBT(16);
     // W^-1: Gauss-Jordan with partial pivoting, lane q < 12 holding row q of [W | I]
     {
       float a[2 * kC];
@@ -512,7 +493,6 @@ __global__ __launch_bounds__(kThreads, 1) void cglow_bwd_kernel(
 #pragma unroll
         for (int j = 0; j < kC; ++j) S.wi[p][mycol * kC + j] = a[kC + j];
     }
-    CBT(17);
     // resize_x: conv3x3 (3 -> 16) at this position's 2x2 block of the 8x8 grid, ReLU, conv 2x2/2
     // (16 -> 6), ReLU
     auto resize1 = [&](float (&h)[4][16]) {
@@ -556,7 +536,6 @@ __global__ __launch_bounds__(kThreads, 1) void cglow_bwd_kernel(
       }
     }
     __syncthreads();
-    CBT(3);
     float fin[kC];
     {  // conv3x3 (6 -> 6), ReLU
       float a[kCh];
@@ -581,7 +560,6 @@ __global__ __launch_bounds__(kThreads, 1) void cglow_bwd_kernel(
 #pragma unroll
     for (int c = 0; c < kC; ++c) S.fin[p][q][c] = fin[c];
     __syncthreads();
-    CBT(4);
     // f: Conv2dNormy(12 -> 8, 3x3) ReLU, Conv2dNormy(8 -> 8, 1x1) ReLU, Conv2dZerosy(8 -> 12) tanh
     float g1[kYH], g2[kYH], u[kC], h[kC];
     {
@@ -681,7 +659,6 @@ __global__ __launch_bounds__(kThreads, 1) void cglow_bwd_kernel(
       }
     }
     __syncthreads();
-    CBT(5);
     {  // f4w: dW[o][n = (t9, c)] = sum_(p,q) D[p][q][o] g2[p][q + tap][c] (K = 256): column
        // tiles w, and 4 in wave 0
       auto job = [&](f4 &cc, int nt) {
@@ -750,7 +727,6 @@ __global__ __launch_bounds__(kThreads, 1) void cglow_bwd_kernel(
 #pragma unroll
     for (int o = 0; o < kYH; ++o) S.D[p][q][o] = d2[o];
     __syncthreads();
-    CBT(6);
     if (w == 1) {  // f2w: dW[o][c] = sum_(p,q) D[p][q][o] g1[p][q][c]
       const bool ok = lr < kYH;
       const int o = ok ? lr : 0;
@@ -852,7 +828,6 @@ __global__ __launch_bounds__(kThreads, 1) void cglow_bwd_kernel(
 #pragma unroll
     for (int o = 0; o < kCh; ++o) S.D[p][q][o] = d4[o];
     __syncthreads();
-    CBT(7);
     {  // r4w: dW[o][n = (t9, c)] = sum D[p][q][o] r2[p][q + tap][c]: column tile w (54 columns)
       const int n = w * 16 + lr, t9 = n / kCh, ch = n % kCh, dr = t9 / 3 - 1, ds = t9 % 3 - 1;
       const bool nok = n < 9 * kCh, mok = lr < kCh;
@@ -897,7 +872,6 @@ __global__ __launch_bounds__(kThreads, 1) void cglow_bwd_kernel(
       if (q == 0) S.sm[p][24 + o] = a;
     }
     __syncthreads();  // D (r4), g1 / g2 (aliased by R1) no longer read; sm complete
-    CBT(8);
     contract<kOffF + Aff::r2b>(acc, [&](int j) {
       float a = 0.f;
       _Pragma("unroll 1") for (int pp = 0; pp < kTP; ++pp) a += S.sm[pp][24 + j];
@@ -942,7 +916,6 @@ __global__ __launch_bounds__(kThreads, 1) void cglow_bwd_kernel(
         *reinterpret_cast<f4 *>(&S.R1[p4][q][ab][4 * w]) = v;
       }
       __syncthreads();
-      if (rw == 0) CBT(13);
       {  // r2w: dW[o][n = (ab, c)] = sum_(p4,q) D[4 rw + p4][q][o] r1[p4][q][ab][c]: tile ab = w
         const bool mok = lr < kCh;
         const int orow = mok ? lr : 0;
@@ -954,7 +927,6 @@ __global__ __launch_bounds__(kThreads, 1) void cglow_bwd_kernel(
         }
       }
       __syncthreads();
-      if (rw == 0) CBT(14);
       {  // d r1 of this lane's entries (read, then overwritten in place), per-particle sums (r0b)
         float dd[kCh];
 #pragma unroll
@@ -982,7 +954,6 @@ __global__ __launch_bounds__(kThreads, 1) void cglow_bwd_kernel(
         }
       }
       __syncthreads();
-      if (rw == 0) CBT(15);
       {  // r0w: dW[o][t] = sum_(p4, 8x8 pos) d1[p4][pos][o] x[p4][c][pos + tap]; wave w: column
          // tile w & 1, particles 2 (w >> 1) .. +1 of the round (the halves are added at the end)
         const int n = (w & 1) * 16 + lr, dr = n / 9 - 1, ds = (n / 3) % 3 - 1, c = n % 3;
@@ -1020,7 +991,6 @@ __global__ __launch_bounds__(kThreads, 1) void cglow_bwd_kernel(
         for (int c = 0; c < 3; ++c) S.gX[pp][c * 64 + r * 8 + s8] += a[c];
       }
       __syncthreads();
-      CBT(9);
     }
     contract<kOffF + Aff::r0b>(acc, [&](int j) {
       float a = 0.f;
@@ -1067,7 +1037,6 @@ __global__ __launch_bounds__(kThreads, 1) void cglow_bwd_kernel(
       }
     }
     __syncthreads();
-    CBT(10);
     // ---------------- conditioning nets backward (A: actnorm, I: 1x1 conv) ----------------
     for (int idx = q; idx < 2 * kC + kC * kC; idx += 16) {  // through the tanh
       const bool isI = idx >= 2 * kC;
@@ -1291,7 +1260,6 @@ __global__ __launch_bounds__(kThreads, 1) void cglow_bwd_kernel(
       S.gX[p][ci * 64 + (2 * qi + a2) * 8 + 2 * qj + b2] += a;
     }
     __syncthreads();
-    CBT(11);
     // ---------------- the condition's gradient: out, or through the particle encoder ----------------
     if (!PART || SQZ) {
       if (valid)
@@ -1377,7 +1345,6 @@ __global__ __launch_bounds__(kThreads, 1) void cglow_bwd_kernel(
       }
     }
     __syncthreads();
-    CBT(12);
   }
   // this workgroup's parameter-gradient row
   float *row = partial + (int64_t)blockIdx.x * kTotParams;
@@ -1521,12 +1488,6 @@ static int launch_chain(const float *pe, const float *glow, int K, const float *
 }  // namespace nfdpf
 
 using namespace nfdpf;
-
-#ifdef NFDPF_EXP_CBTRACE
-extern "C" NFDPF_API int nfdpf_exp_cbtrace_read(void *host) {
-  return hipMemcpyFromSymbol(host, HIP_SYMBOL(cgb::g_cbtrace), sizeof(cgb::g_cbtrace)) == hipSuccess ? 0 : 1;
-}
-#endif
 
 extern "C" int64_t nfdpf_cglow_backward_workspace(int64_t M) {
   if (M < 0) return -1;

@@ -75,34 +75,6 @@ struct PassHdr {
   uint32_t done;
 };
 
-#ifdef NFDPF_EXP_PTRACE
-// experiment-only: per-step phase timestamps (s_memrealtime, 100 MHz) of waves 0, 1 and 8 of
-// every workgroup, steps < 64 (scripts/archive/exp_ptrace.py)
-__device__ unsigned long long g_ptrace[256][16][64][20];
-#define PT(t, k)                                                                                   \
-  do {                                                                                             \
-    const int w_ = threadIdx.x >> 6, wi_ = w_;          \
-    const int wg_ = (b) * gridDim.x + (tile); /* logical (row, tile) */                              \
-    if (wi_ >= 0 && (threadIdx.x & 63) == 0 && wg_ < 256 && (t) < 64)                             \
-      g_ptrace[wg_][wi_][(t)][(k)] = __builtin_amdgcn_s_memrealtime();                             \
-  } while (0)
-#else
-#define PT(t, k) \
-  do {           \
-  } while (0)
-#endif
-
-// SPEC: the prior wave, not the chain, stores the step's histories (hist_x, noise, index, jac):
-// five vector stores per step off the chain's critical path (experiment knob)
-#ifndef NFDPF_PASS_HSTORE
-#define NFDPF_PASS_HSTORE 1
-#endif
-// SPEC: the next step's motion and exchange A published at the end of the step, before its
-// commit (A/B: pass 0.595-0.614 vs 0.621-0.630 ms, three pairs on one box)
-#ifndef NFDPF_PASS_PRE
-#define NFDPF_PASS_PRE 1
-#endif
-
 // pass modes (tiled_pass_kernel<MODE>)
 constexpr int kModeSpec = 0;   // every ESS gate taken as off (verified after the pass)
 constexpr int kModeForce = 1;  // --force-resample: the row resampled at the top of every step
@@ -197,9 +169,7 @@ struct PassLds {
   int qf[4], rf[4];
   alignas(8) int pf[4];
   alignas(8) int ef[8];
-#if NFDPF_PASS_HSTORE
   float ebuf[2][3 * kTile];        // SPEC: the chain's motion noise and log|det J|, to the prior wave
-#endif
   float lr_l[kTile];               // FORCE / GATE: this tile's resampled log-weights (outside the union:
                                    // the encoder waves read it while others may start their MFMA layers)
   int fS, fbar;                    // FORCE: resampling done, flow-wave barrier
@@ -252,10 +222,6 @@ struct Spin {
   uint64_t t0 = 0;
   int it = 0;
 };
-#ifndef NFDPF_PASS_FLAG_SLEEP
-#define NFDPF_PASS_FLAG_SLEEP 1
-#endif
-template <int SLEEP = 1>
 __device__ __forceinline__ bool pass_spin(Spin &s) {
   if ((s.it++ & 63) == 0) {
     int *abort_w = &kernarg_ws()->hdr->abort;
@@ -271,14 +237,14 @@ __device__ __forceinline__ bool pass_spin(Spin &s) {
       return false;
     }
   }
-  __builtin_amdgcn_s_sleep(SLEEP);
+  __builtin_amdgcn_s_sleep(1);
   return true;
 }
 
 // wait until the LDS flag reaches v (wave-uniform)
 __device__ __forceinline__ void wait_flag(const int *f, int v) {
   Spin s;
-  while (__builtin_amdgcn_readfirstlane(*(lds_vint *)f) < v && pass_spin<NFDPF_PASS_FLAG_SLEEP>(s)) {
+  while (__builtin_amdgcn_readfirstlane(*(lds_vint *)f) < v && pass_spin(s)) {
   }
   asm volatile("" ::: "memory");
 }
@@ -286,9 +252,6 @@ __device__ __forceinline__ void wait_flag(const int *f, int v) {
 __device__ __forceinline__ void set_flag(int *f, int v) {
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   *(lds_vint *)f = v;
-#ifdef NFDPF_PASS_WAKE
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_wakeup" ::: "memory");
-#endif
 }
 
 // four wave-uniform doubles as 8 granules (lanes 0..7: value l / 2, low / high word by l & 1)
@@ -386,7 +349,7 @@ __device__ __forceinline__ void wait_flag2(const int *f, int v) {
   for (;;) {
     const uint64_t w = *(volatile __attribute__((address_space(3))) uint64_t *)f;
     const int a = __builtin_amdgcn_readfirstlane((int)(uint32_t)w), c = __builtin_amdgcn_readfirstlane((int)(w >> 32));
-    if ((a >= v && c >= v) || !pass_spin<NFDPF_PASS_FLAG_SLEEP>(s)) break;
+    if ((a >= v && c >= v) || !pass_spin(s)) break;
   }
   asm volatile("" ::: "memory");
 }
@@ -425,9 +388,6 @@ __device__ __forceinline__ void flow_barrier(int *cnt, int &round) {
   round += 8;
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   if ((threadIdx.x & 63) == 0) atomicAdd(cnt, 1);
-#ifdef NFDPF_PASS_WAKE
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_wakeup" ::: "memory");
-#endif
   wait_flag(cnt, round);
 }
 
@@ -448,16 +408,13 @@ __device__ __forceinline__ void flow_barrier(int *cnt, int &round) {
 // encoder wave 0 to have published C(t-1) or a later C.
 // fR(t-1) also means that every encoder wave of this tile has finished its MFMA layers of step
 // t-1 (it publishes C(t-1) after them): the resampling scratch (PassRs) aliases their LDS.
-#ifndef NFDPF_GATE_LATE
-#define NFDPF_GATE_LATE 1
-#endif
-// late = true (FORCE; GATE unless NFDPF_GATE_LATE=0): the tail needs no barrier -- each chain
-// wave gathers its own slots' sources (slot == tid) and reads them back itself, and wave 7, a
+// The tail needs no barrier -- each chain wave
+// gathers its own slots' sources (slot == tid) and reads them back itself, and wave 7, a
 // prior wave idle until the proposal, sums the gathered weights and writes lr_l, then raises fS:
 // the encoder waves wait for fS before their MFMA layers reuse this scratch (GATE: after the
 // chain's commit, when step t or t - 1 fired).
 __device__ __forceinline__ void pass_resample(const nfdpf_filter_desc &d, const PassWs &ws, PassLds &L, int b,
-                                              int tile, uint32_t tag0, int t, int &round, bool late) {
+                                              int tile, uint32_t tag0, int t, int &round) {
   PassRs &R = L.rs;
   const int N = d.N, tiles = n_tiles(N), tid = threadIdx.x, nth = 8 * 64;
   const int64_t grow = d.row_base + b;
@@ -479,7 +436,6 @@ __device__ __forceinline__ void pass_resample(const nfdpf_filter_desc &d, const 
   };
   if (t > 0) {
     wait_flag(&L.fR, t);  // wave 8 has swept C(t - 1): slot t - 1's row normaliser in L.rn
-    PT(t, 12);
     const RowNorm rn = L.rn[(t - 1) & 1];
     const float *us = ws.gu + ((int64_t)((t - 1) & 1) * d.B + b) * N;
     for (int j = tid; j < N; j += nth) put(j, expf(load_wt(us + j) - rn.shift) / rn.Ssum + 1e-12f);  // pass_norm's p
@@ -491,20 +447,16 @@ __device__ __forceinline__ void pass_resample(const nfdpf_filter_desc &d, const 
     xs_next = d.x_prev_rs;
   }
   flow_barrier(&L.fbar, round);
-  PT(t, 13);
   // SoftRow's q and w on the stored q_raw (the same values, not recomputed)
   auto qv = [&](int j) { return mix ? R.qr[j] / row.S : R.pl[j]; };
   auto wv = [&](int j) { return mix ? R.pl[j] / qv(j) : row.u; };
   if (mix) {
     if (tid < 64) {
-      PT(t, 19);
       const float S = (N >= 8 ? cascade_row_sum_1k<kPassMaxTiles * kTile>([&](int j) { return R.qr[j]; }, N)
                               : cascade_row_sum([&](int j) { return R.qr[j]; }, N));
       if (tid == 0) R.shf[0] = S;
-      PT(t, 11);
     }
     flow_barrier(&L.fbar, round);
-  PT(t, 14);
     row.S = R.shf[0];
   }
   // the exact f64 prefix of q: 2 consecutive j per thread (N <= 1024), wave scans, wave order
@@ -528,7 +480,6 @@ __device__ __forceinline__ void pass_resample(const nfdpf_filter_desc &d, const 
     }
     if (lane == 63) R.shd[w] = inc;
     flow_barrier(&L.fbar, round);
-  PT(t, 15);
     double base = 0.0, sh[8];  // (the 8 wave totals loaded at once, then added in wave order)
 #pragma unroll
     for (int k = 0; k < 8; ++k) sh[k] = R.shd[k];
@@ -546,7 +497,6 @@ __device__ __forceinline__ void pass_resample(const nfdpf_filter_desc &d, const 
     }
   }
   flow_barrier(&L.fbar, round);
-  PT(t, 16);
   const int i0 = tile * kTile;
   {  // markers tid and tid + 512 (N <= 1024), their two searches interleaved (two LDS probes in
      // flight per step instead of one search after the other); the same lower bound
@@ -575,9 +525,7 @@ __device__ __forceinline__ void pass_resample(const nfdpf_filter_desc &d, const 
       if (ib >= i0 && ib < i0 + kTile) R.src_l[ib - i0] = sj;
     }
   }
-  PT(t, 6);
   flow_barrier(&L.fbar, round);
-  PT(t, 17);
   // the tile's sources' positions (their loads in flight while wave 0 sums the gathered weights),
   // then wave 0 turns every particle of the tile into its resampled log-weight
   if (tid < kTile && i0 + tid < N) {
@@ -606,20 +554,16 @@ __device__ __forceinline__ void pass_resample(const nfdpf_filter_desc &d, const 
     R.xr_l[tid][0] = x0;
     R.xr_l[tid][1] = x1;
   }
-  PT(t, 10);
-  const int sw = late ? nth - 64 : 0;  // the wave that sums the gathered weights
+  const int sw = nth - 64;  // the wave that sums the gathered weights
   if (tid >= sw && tid < sw + 64) {
     const float s2 = (N >= 8 ? cascade_row_sum_1k<kPassMaxTiles * kTile>([&](int j) { return R.wg[j]; }, N)
                              : cascade_row_sum([&](int j) { return R.wg[j]; }, N));
-    PT(t, 9);
 #pragma unroll
     for (int k = 0; k < kTile / 64; ++k) {
       const int s = k * 64 + tid - sw;
       if (i0 + s < N) L.lr_l[s] = logf(R.wg[i0 + s] / s2);
     }
   }
-  if (!late) flow_barrier(&L.fbar, round);
-  PT(t, 18);
   if (tid >= sw && tid < sw + 64) set_flag(&L.fS, t + 1);  // the encoder waves may read lr_l
 }
 
@@ -678,18 +622,13 @@ static void pass_launch_rows(K kern, const nfdpf_filter_desc &d, PassWs ws, int 
 // launches' layout also multiplies by 2 log2(e) and evaluates 1 - 2 r (two packed ops per unit
 // pair more).  Layer 3 summed the way split.hpp's net_split sums it (even and odd hidden units in
 // two chains, then (even + odd) + b3).  cb = the half's folded bias pairs (fold_ref order).
-#ifndef NFDPF_PASS_SB
-#define NFDPF_PASS_SB 1
-#endif
 // {1 / (1 + 2^y.x), 1 / (1 + 2^y.y)}: 2^y = inf -> 0, 2^y = 0 -> 1 (no NaN anywhere)
 __device__ __forceinline__ f2 sig2(f2 y) {
   const f2 d = f2{__builtin_amdgcn_exp2f(y.x), __builtin_amdgcn_exp2f(y.y)} + splat(1.0f);
   return f2{__builtin_amdgcn_rcpf(d.x), __builtin_amdgcn_rcpf(d.y)};
 }
 __device__ __forceinline__ f2 ts_half(cf2 *w, float u, const f2 *cb) {
-#if NFDPF_PASS_SB
   __builtin_amdgcn_sched_barrier(0);  // no weight loads hoisted from here into the previous half
-#endif
   f2 h[kH];
 #pragma unroll
   for (int j = 0; j < kH; ++j) h[j] = sig2(pfma(w[j], splat(u), cb[j]));
@@ -824,8 +763,10 @@ __device__ __forceinline__ void pass_chain(const nfdpf_filter_desc &d, const Pas
   // the step's velocity, loaded one step ahead (beside the next step's noise): no scalar-load
   // latency at the head of the step
   float nv0 = d.vel[2 * (int64_t)b], nv1 = d.vel[2 * (int64_t)b + 1];
-  // SPEC (NFDPF_PASS_PRE): the next step's x_phys / noise, its A already published (pre)
-  constexpr bool PRE = NFDPF_PASS_PRE && MODE == kModeSpec;
+  // SPEC: the next step's motion and exchange A published at the end of the step, before its
+  // commit (A/B: pass 0.595-0.614 vs 0.621-0.630 ms, three pairs on one box): the next step's
+  // x_phys / noise, its A already published (pre)
+  constexpr bool PRE = MODE == kModeSpec;
   float pp0 = 0.f, pp1 = 0.f, pe0 = 0.f, pe1 = 0.f;
   bool pre = false;
   const int i_ = i, slot_ = slot;
@@ -837,7 +778,6 @@ __device__ __forceinline__ void pass_chain(const nfdpf_filter_desc &d, const Pas
     const int par = t & 1;
     const uint32_t tag = tag0 + (uint32_t)t + 1u;
     const float v0 = nv0, v1 = nv1;
-    PT(t, 0);
     if (t == 0 && valid) pass_noise(d, 0, grow, i, en0, en1);
     // the step's input particles: own (x0, x1) or the row's resampling's
     float xs0 = x0, xs1 = x1;
@@ -861,7 +801,7 @@ __device__ __forceinline__ void pass_chain(const nfdpf_filter_desc &d, const Pas
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         set_flag(&L.hxf[g], t);
       }
-      pass_resample(d, ws, L, b, tile, tag0, t, round, FORCE || NFDPF_GATE_LATE);
+      pass_resample(d, ws, L, b, tile, tag0, t, round);
       if (GATE) {
         fire = plan ? pred : wait_dec(L, t);
         known = true;
@@ -897,7 +837,6 @@ __device__ __forceinline__ void pass_chain(const nfdpf_filter_desc &d, const Pas
           publish4(ws.ga + gslot * kGA, s, tag);
         }
       }
-      PT(t, 1);
       // the next step's motion noise, drawn while the A sweep is in flight / fA is awaited
       auto next_noise = [&]() {
         if (first && t + 1 < d.T) {
@@ -920,7 +859,6 @@ __device__ __forceinline__ void pass_chain(const nfdpf_filter_desc &d, const Pas
           asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
           set_flag(&L.hxf[g], t);
         }
-        PT(t, 7);
         if (st == 0) {
           const Ctx4 c = row_ctx(L.rowa, tiles, inv_n, inv_n1);
           if (fold_lane) {
@@ -942,7 +880,6 @@ __device__ __forceinline__ void pass_chain(const nfdpf_filter_desc &d, const Pas
         wait_flag(&L.fA, fa);
         if (spec && __builtin_amdgcn_readfirstlane(*(lds_vint *)&L.fA) == fa + 1) return 2;
       }
-      PT(t, 2);
       // nf_dyn inverse (model/models.py:305-332)
       cf2 *dyn = wptr2(d.dyn_params), *cond = wptr2(d.cond_params);
       float xd0 = p0, xd1 = p1, ld = 0.f;
@@ -950,7 +887,6 @@ __device__ __forceinline__ void pass_chain(const nfdpf_filter_desc &d, const Pas
         for (int f = nfl - 1; f >= 0; --f)
           ld += pass_inverse(dyn + f * 2 * nsd, nsd, xd0, xd1, L.cbd[par] + f * 2 * kH);
       jac = -ld;
-      PT(t, 3);
       {
         double s[4] = {valid ? xd0 : 0.0, valid ? xd1 : 0.0, valid ? (double)xd0 * xd0 : 0.0,
                        valid ? (double)xd1 * xd1 : 0.0};
@@ -961,7 +897,6 @@ __device__ __forceinline__ void pass_chain(const nfdpf_filter_desc &d, const Pas
         if (!HOLD && fold_lane) load_fwc(d);
         const int st = poll_rowx<3>(ws.gb + grow0 * kGA, tiles * 4 * kGA, tag, L.rowa, NoWork(), stop);
         if (st == 0) {
-          PT(t, 8);
           const Ctx4 c = row_ctx(L.rowa, tiles, inv_n, inv_n1);
           wait_flag(&L.fE, t + 1);
           if (fold_lane) {
@@ -978,7 +913,6 @@ __device__ __forceinline__ void pass_chain(const nfdpf_filter_desc &d, const Pas
         wait_flag(&L.fB, fa);
         if (spec && __builtin_amdgcn_readfirstlane(*(lds_vint *)&L.fB) == fa + 1) return 2;
       }
-      PT(t, 4);
       // NF proposal inverse (model/models.py:334-356)
       q0 = xd0;
       q1 = xd1;
@@ -1010,16 +944,17 @@ __device__ __forceinline__ void pass_chain(const nfdpf_filter_desc &d, const Pas
       if (!GATE || known) break;
       // the speculated step's decision: commit, or drop the attempt and redo after resampling
       fire = wait_dec(L, t);
-      PT(t, 9);
       known = true;
       if (!fire) break;
       if (w == 0) set_flag(&L.rq, t + 1);  // the prior waves join the row's resampling
-      pass_resample(d, ws, L, b, tile, tag0, t, round, FORCE || NFDPF_GATE_LATE);
+      pass_resample(d, ws, L, b, tile, tag0, t, round);
       take_resampled();
       variant = 1;
     }
     // commit step t: the histories, and the proposal to the prior wave and the encoder pair
-    constexpr bool HS = NFDPF_PASS_HSTORE && MODE == kModeSpec;  // the prior wave stores them
+    // SPEC: the prior wave, not the chain, stores the step's histories (hist_x, noise, index,
+    // jac): five vector stores per step off the chain's critical path
+    constexpr bool HS = MODE == kModeSpec;
     const RowSlot S = row_slot(d, b, t);
     if (valid && !HS) {
       S.hnoise[2 * i] = e0;
@@ -1029,22 +964,18 @@ __device__ __forceinline__ void pass_chain(const nfdpf_filter_desc &d, const Pas
     }
     // the group's encoder pair has read qbuf / rbuf[par] of step t - 2 (HS: its prior wave ebuf)
     if (t >= 2) wait_flag2(&L.ef[2 * g], t - 1);
-#if NFDPF_PASS_HSTORE
     if (HS && t >= 2) wait_flag(&L.pf[g], t - 1);
-#endif
     if (valid) {  // to the prior wave and the encoder pair
       L.qbuf[par][slot] = q0;
       L.qbuf[par][kTile + slot] = q1;
       L.pbuf[par][slot] = p0 - e0;
       L.pbuf[par][kTile + slot] = p1 - e1;
       L.rbuf[par][kTile + slot] = (density(e0, e1, K, two_var) + jac) + (-ldp);  // propose
-#if NFDPF_PASS_HSTORE
       if (HS) {
         L.ebuf[par][slot] = e0;
         L.ebuf[par][kTile + slot] = e1;
         L.ebuf[par][2 * kTile + slot] = jac;
       }
-#endif
       if (FORCE || GATE) {  // a later step's resampling reads the row's particles from other tiles
         store_wt2(S.hx + 2 * i, q0, q1);
       } else if (!HS) {
@@ -1056,7 +987,6 @@ __device__ __forceinline__ void pass_chain(const nfdpf_filter_desc &d, const Pas
     // by the next step's A sweep / resampling, hxf)
     if (FORCE) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     set_flag(&L.qf[g], t + 1);
-    PT(t, 5);
     x0 = q0;
     x1 = q1;
     if (GATE) gp.update(fire);
@@ -1096,8 +1026,7 @@ __device__ __forceinline__ void pass_prior(const nfdpf_filter_desc &d, const Pas
     const RowSlot S = row_slot(d, b, t);
     const int32_t *plan = GATE ? d.pass_plan : nullptr;
     const int pred = GATE ? (plan ? (plan[t] ? 1 : 0) : t == 0 ? wait_dec(L, 0) : gp.get()) : 0;
-    if (FORCE || pred) pass_resample(d, ws, L, b, tile, tag0, t, round, FORCE || NFDPF_GATE_LATE);
-    PT(t, 0);
+    if (FORCE || pred) pass_resample(d, ws, L, b, tile, tag0, t, round);
     if (g == 0) {
       // the proposal fold over the encoding columns (model/models.py:338-346) one step ahead,
       // while this wave waits for the proposal: step t + 1's (and step 0's at t = 0), so wave
@@ -1119,18 +1048,16 @@ __device__ __forceinline__ void pass_prior(const nfdpf_filter_desc &d, const Pas
       for (;;) {
         const int q = __builtin_amdgcn_readfirstlane(*(lds_vint *)&L.qf[g]);
         const int r = __builtin_amdgcn_readfirstlane(*(lds_vint *)&L.rq);
-        if (q >= t + 1 || r >= t + 1 || !pass_spin<NFDPF_PASS_FLAG_SLEEP>(sp)) break;
+        if (q >= t + 1 || r >= t + 1 || !pass_spin(sp)) break;
       }
       asm volatile("" ::: "memory");
       if (__builtin_amdgcn_readfirstlane(*(lds_vint *)&L.rq) >= t + 1)
-        pass_resample(d, ws, L, b, tile, tag0, t, round, FORCE || NFDPF_GATE_LATE);
+        pass_resample(d, ws, L, b, tile, tag0, t, round);
     }
     wait_flag(&L.qf[g], t + 1);
-    PT(t, 1);
     if (valid) {
       float lo = L.qbuf[par][slot], up = L.qbuf[par][kTile + slot], ld2 = 0.f;
       const float r0 = L.pbuf[par][slot], r1 = L.pbuf[par][kTile + slot];
-#if NFDPF_PASS_HSTORE
       if constexpr (MODE == kModeSpec) {  // the chain's histories of step t (pass_chain's commit)
         S.hx[2 * i] = lo;
         S.hx[2 * i + 1] = up;
@@ -1139,12 +1066,7 @@ __device__ __forceinline__ void pass_prior(const nfdpf_filter_desc &d, const Pas
         S.hidx[i] = (int64_t)N * (d.row_base + b) + i;
         if (S.hjac) S.hjac[i] = L.ebuf[par][2 * kTile + slot];
       }
-#endif
-#ifndef NFDPF_EXP_NOFWD
       for (int f = 0; f < nfl; ++f)
-#else
-      for (int f = 0; f < nfl && lo == 12345.f; ++f)  // experiment only: timing without the prior's forward
-#endif
         ld2 += pass_forward(dyn + f * 2 * nsd, nsd, lo, up, L.cbd[par] + f * 2 * kH);
       const float prior = density(lo - r0, up - r1, K, two_var) - (-ld2);
       L.rbuf[par][slot] = prior;
@@ -1153,7 +1075,6 @@ __device__ __forceinline__ void pass_prior(const nfdpf_filter_desc &d, const Pas
     set_flag(&L.rf[g], t + 1);
     set_flag(&L.pf[g], t + 1);
     if (GATE) gp.update(__builtin_amdgcn_readfirstlane(*(lds_vint *)&L.dec[par]));  // committed: known
-    PT(t, 2);
   }
 }
 
@@ -1322,39 +1243,13 @@ __device__ __forceinline__ float pass_norm(const nfdpf_filter_desc &d, const Pas
 // resampled log-weight of its particle's source (lr_l) instead of its own log p
 // issue priority: the chain waves carry the pass's critical path (chain 3 / others 0: +0.8 %
 // at C2 over equal priorities, two A/B rounds on one box)
-#ifndef NFDPF_PRIO_CHAIN
-#define NFDPF_PRIO_CHAIN 3
-#define NFDPF_PRIO_PRIOR 0
-#define NFDPF_PRIO_ENC 0
-#endif
-#ifndef NFDPF_GPRIO_PRIOR
-#define NFDPF_GPRIO_PRIOR 0
-#endif
-// Which encoder wave sweeps exchange C (and, GATE, decides the gate), and the issue priority it
-// takes meanwhile: in the gated and forced passes that sweep is on the step's critical path
-// (the decision / the row's resampling wait for it), while its SIMD also carries a chain wave
-// at priority 3.
-#ifndef NFDPF_SWEEP_WE
-#define NFDPF_SWEEP_WE 0
-#endif
-#ifndef NFDPF_SWEEP_PRIO
-#define NFDPF_SWEEP_PRIO 0
-#endif
-template <int MODE>
-__device__ __forceinline__ void sweep_prio(bool on) {
-  if constexpr (MODE != kModeSpec && NFDPF_SWEEP_PRIO != 0) {
-    if (on)
-      __builtin_amdgcn_s_setprio(NFDPF_SWEEP_PRIO);
-    else
-      __builtin_amdgcn_s_setprio(NFDPF_PRIO_ENC);
-  }
-}
+constexpr int kPrioChain = 3, kPrioOther = 0;
 
 template <int MODE, bool XR = false>
 __device__ __forceinline__ void pass_encoder(const nfdpf_filter_desc &d, const PassWs &ws, PassLds &L, int b, int tile,
                                              uint32_t tag0) {
   constexpr bool FORCE = MODE == kModeForce, GATE = MODE == kModeGate;
-  const int sweeper = MODE == kModeSpec ? 0 : NFDPF_SWEEP_WE;  // (encoder-wave index, 0..7)
+  constexpr int sweeper = 0;  // the encoder wave (index 0..7) that sweeps exchange C and, GATE, decides the gate
   const int tiles = n_tiles(d.N), N = d.N;
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, we = w - 8;
   const int role = w & 1, g = (w >> 1) & 3;
@@ -1375,7 +1270,6 @@ __device__ __forceinline__ void pass_encoder(const nfdpf_filter_desc &d, const P
     const int i_e = MODE == kModeSpec ? i_e_ : opaque_int(i_e_);
     const int par = t & 1;
     const float *enc_t = d.enc + ((int64_t)b * d.T + t) * d.E;
-    PT(t, 0);
     // measure_row_setup (cosine), per wave into its own LDS copy
     const float ve = lane < kE ? enc_t[lane] : 0.f;
     const double vinv = 1.0 / fmax(sqrt(wave_sum((double)ve * ve)), 1e-12);
@@ -1393,14 +1287,8 @@ __device__ __forceinline__ void pass_encoder(const nfdpf_filter_desc &d, const P
       if (GATE && (d.pass_plan ? d.pass_plan[t] != 0
                                : ((t > 0 && gp.get()) || __builtin_amdgcn_readfirstlane(*(lds_vint *)&L.dec[par]) != 0)))
         wait_flag(&L.fS, t + 1);
-      PT(t, 4);
-#ifndef NFDPF_EXP_NOENC
       encode_dot_mfma_half<kE>(ef, role, L.qbuf[par] + g * 64, L.qbuf[par] + kTile + g * 64, L.encq[we], ss, dot,
                                L.Hws[we]);
-#else
-      ss = 1.0; dot = 0.5;  // experiment only: timing without the encoder
-#endif
-      PT(t, 5);
       return cos_lik(ss, dot, vinv);
     };
     float lk = 0.f;
@@ -1408,16 +1296,12 @@ __device__ __forceinline__ void pass_encoder(const nfdpf_filter_desc &d, const P
       // the encoder first: it needs only the proposal, and it hides the C(t - 1) exchange
       if (grp) lk = encode();
       if (we == 0 && t > 0) pass_poll_c(d, ws, L, b, tile, tag0, t - 1);
-      PT(t, 2);
       if (t > 0) lr = pass_norm(d, ws, L, b, tile, t - 1, i_e, valid_e, u, qx0, qx1);
     } else if constexpr (FORCE) {
       // the row's resampling at the top of step t needs slot t - 1 normalised first (fR(t - 1))
       if (we == sweeper && t > 0) {
-        sweep_prio<MODE>(true);
         pass_poll_c(d, ws, L, b, tile, tag0, t - 1);
-        sweep_prio<MODE>(false);
       }
-      PT(t, 2);
       if (t > 0) lr = pass_norm(d, ws, L, b, tile, t - 1, i_e, valid_e, u, qx0, qx1);
       wait_flag(&L.fS, t + 1);  // the flow waves resampled the row: the log-weight of the source
       lr = valid_e ? L.lr_l[slot_e] : 0.f;
@@ -1426,13 +1310,9 @@ __device__ __forceinline__ void pass_encoder(const nfdpf_filter_desc &d, const P
       // GATE: slot t - 1's exchange, its normaliser and step t's decision first (the chain's
       // speculation of step t waits for it), then the measurement
       if (we == sweeper && t > 0) {
-        sweep_prio<MODE>(true);
         const float inv = pass_poll_c(d, ws, L, b, tile, tag0, t - 1);
-        PT(t, 10);
         pass_gate<XR>(d, ws, L, b, tile, tag0, t, inv);
-        sweep_prio<MODE>(false);
       }
-      PT(t, 2);
       if (t > 0) lr = pass_norm(d, ws, L, b, tile, t - 1, i_e, valid_e, u, qx0, qx1);
       if (grp) lk = encode();
       // step t is committed (qf): its decision is known; a fired gate resampled the row and
@@ -1442,7 +1322,6 @@ __device__ __forceinline__ void pass_encoder(const nfdpf_filter_desc &d, const P
       gp.update(pdec);
     }
     // the log-weight (DPFs.py:187)
-    PT(t, 3);
     u = 0.f;
     if (grp) {
       if (valid_e) {
@@ -1454,7 +1333,6 @@ __device__ __forceinline__ void pass_encoder(const nfdpf_filter_desc &d, const P
       if (valid_e) u = logw(lr, lk, L.rbuf[par][slot_e], L.rbuf[par][kTile + slot_e]);
     }
     set_flag(&L.ef[we], t + 1);  // qbuf / rbuf[par] read: the chain wave may reuse them at t + 2
-    PT(t, 6);
     if (FORCE || GATE) {  // the row's next resampling reads u from every tile: written through, drained
       if (valid_e) store_wt(ws.gu + ((int64_t)par * d.B + b) * N + i_e, u);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1476,7 +1354,6 @@ __device__ __forceinline__ void pass_encoder(const nfdpf_filter_desc &d, const P
       const int64_t gslot = (((int64_t)par * d.B + b) * tiles + tile) * 8 + we;
       gran_store(ws.gc + gslot * kGC + lane, word, tag0 + (uint32_t)t + 1u);
     }
-    PT(t, 7);
   }
   // the last slot's normalisation
   if (we == sweeper) pass_poll_c(d, ws, L, b, tile, tag0, d.T - 1);
@@ -1501,16 +1378,13 @@ __global__ __launch_bounds__(4 * kTile, 1) void tiled_pass_kernel(const nfdpf_fi
   if (threadIdx.x == 0) L.fA = L.fB = L.fE = L.fR = L.fS = L.fbar = L.fD = L.rq = 0;
   __syncthreads();
   if (threadIdx.x < 4 * 64) {
-    __builtin_amdgcn_s_setprio(NFDPF_PRIO_CHAIN);
+    __builtin_amdgcn_s_setprio(kPrioChain);
     pass_chain<MODE>(d, ws, L, b, tile, tag0);
   } else if (threadIdx.x < 8 * 64) {
-    if constexpr (MODE == kModeSpec)
-      __builtin_amdgcn_s_setprio(NFDPF_PRIO_PRIOR);
-    else  // the prior's nf_dyn forward feeds the weights every decision / resampling waits for
-      __builtin_amdgcn_s_setprio(NFDPF_GPRIO_PRIOR);
+    __builtin_amdgcn_s_setprio(kPrioOther);
     pass_prior<MODE>(d, ws, L, b, tile, tag0);
   } else {
-    __builtin_amdgcn_s_setprio(NFDPF_PRIO_ENC);
+    __builtin_amdgcn_s_setprio(kPrioOther);
     pass_encoder<MODE, XR>(d, ws, L, b, tile, tag0);
   }
 }

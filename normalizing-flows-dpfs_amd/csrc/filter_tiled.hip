@@ -20,16 +20,6 @@
 #include "soft.hpp"
 #include <hip/hip_ext.h>
 
-#ifdef NFDPF_EXP_QTRACE
-// experiment-only: per-WAVE phase timestamps of the quad proposal launch (last step run)
-__device__ unsigned long long g_qtrace[1024][16][16];
-#define QTRACE(P)                                                                           \
-  if ((threadIdx.x & 63) == 0 && blockIdx.y * gridDim.x + blockIdx.x < 1024)                \
-    g_qtrace[blockIdx.y * gridDim.x + blockIdx.x][threadIdx.x >> 6][P] = __builtin_amdgcn_s_memrealtime();
-#else
-#define QTRACE(P)
-#endif
-
 #include "split.hpp"
 #include "crnvp_mfma.hpp"
 
@@ -40,38 +30,13 @@ namespace nfdpf {
 
 constexpr int kTile = 256;  // particles per workgroup, one per lane
 
-#ifdef NFDPF_EXP_TRACE
-// experiment-only: per-workgroup phase timestamps (s_memrealtime, 100 MHz) of one launch
-__device__ unsigned long long g_trace[4][2048][8];
-#define TRACE(K, P)                                                                        \
-  if (threadIdx.x == 0 && blockIdx.y * gridDim.x + blockIdx.x < 2048)                     \
-    g_trace[K][blockIdx.y * gridDim.x + blockIdx.x][P] = __builtin_amdgcn_s_memrealtime();
-// the same from lane 0 of the executing wave (several waves of one workgroup record slots)
-#define TRACEW(K, P)                                                                       \
-  if ((threadIdx.x & 63) == 0 && blockIdx.y * gridDim.x + blockIdx.x < 2048)              \
-    g_trace[K][blockIdx.y * gridDim.x + blockIdx.x][P] = __builtin_amdgcn_s_memrealtime();
-#else
-#define TRACE(K, P)
-#define TRACEW(K, P)
-#endif
-
-// (row b, tile) of this workgroup.  -DNFDPF_XCD_REMAP: blocks are dealt round-robin over the 8
-// XCDs (blocks k and k + 8 share one, MI355X_MICROARCH.md §Workgroup dispatch), so a row's tiles
-// (blocks 4b .. 4b + 3) sat on 4 different L2s; the remap gives each XCD group whole rows, so the
-// row-level data of the previous launch (the row's particles and partials) is read from the
-// reader's own L2.  Any bijection is correct: every kernel derives (b, tile) here.  Measured
-// SLOWER at C2 (2.05e9 vs 2.13e9: both launches ~0.5-0.8 us longer, one box) -- not the default.
+// (row b, tile) of this workgroup.  Any bijection is correct: every kernel derives (b, tile)
+// here.  Blocks are dealt round-robin over the 8 XCDs (blocks k and k + 8 share one,
+// MI355X_MICROARCH.md §Workgroup dispatch), so a row's tiles (blocks 4b .. 4b + 3) sit on 4
+// different L2s.  A remap that gave each XCD group whole rows (the previous launch's row-level
+// data then in the reader's own L2) measured SLOWER at C2 (2.05e9 vs 2.13e9: both launches
+// ~0.5-0.8 us longer, one box); retired, f81620f is the last commit that holds it.
 __device__ __forceinline__ void tile_row(int &b, int &tile) {
-#ifdef NFDPF_XCD_REMAP
-  const int n = gridDim.x * gridDim.y;
-  if ((n & 7) == 0) {
-    const int id = blockIdx.x + gridDim.x * blockIdx.y;
-    const int lin = (id & 7) * (n >> 3) + (id >> 3);
-    tile = lin % gridDim.x;
-    b = lin / gridDim.x;
-    return;
-  }
-#endif
   b = blockIdx.y;
   tile = blockIdx.x;
 }
@@ -82,7 +47,6 @@ struct TiledWs {
   float *cb_dyn;    // [B][kCb] folded nf_dyn biases of the row (K2, tile 0)
   float *cb_cond;   // [B][kCb] proposal fold over the encoding columns (K1, tile 0)
   double *fin;      // [B][T][tiles][4] sum p^2, sum p x0, sum p x1, sum logw
-  uint64_t *rowx;   // [B][tiles][8] the fused step's x_dyn partials as tagged granules
   // tiled_rows_kernel's outputs (long rows, soft resampler): the step's gate, each row's
   // normaliser of the deferred slot t-1 and, when the gate fired, each particle's source and
   // resampled log-weight
@@ -102,7 +66,7 @@ __host__ __device__ static inline int n_tiles(int N) { return (N + kTile - 1) / 
 
 static int64_t tiled_bytes(int B, int N, int T) {
   const int64_t bt = (int64_t)B * n_tiles(N);
-  return al256(bt * 32) * 2 + al256((int64_t)B * kCb * 4) * 2 + al256(bt * T * 32) + al256(bt * 64) + al256(4) +
+  return al256(bt * 32) * 2 + al256((int64_t)B * kCb * 4) * 2 + al256(bt * T * 32) + al256(4) +
          al256((int64_t)B * 16) + al256((int64_t)B * N * 4) * 2;
 }
 
@@ -120,8 +84,6 @@ static TiledWs tiled_carve(void *ws, int B, int N, int T) {
   p += al256((int64_t)B * kCb * 4);
   w.fin = (double *)p;
   p += al256(bt * T * 32);
-  w.rowx = (uint64_t *)p;
-  p += al256(bt * 64);
   w.rs_gate = (int32_t *)p;
   p += al256(4);
   w.rs_rn = (float *)p;
@@ -438,7 +400,6 @@ __global__ __launch_bounds__(kTile) void tiled_front_kernel(const nfdpf_filter_d
   __shared__ int fire_sh;
   __shared__ float xr_sh[ROWS ? 1 : kTile][2];
   __shared__ int src_sh[ROWS ? 1 : kTile];
-  TRACE(0, 0)
   const int tiles = n_tiles(d.N), N = d.N;
   int b, tile;
   tile_row(b, tile);
@@ -458,7 +419,6 @@ __global__ __launch_bounds__(kTile) void tiled_front_kernel(const nfdpf_filter_d
     const int64_t my_row = ess_row(d, b);
     fire = tiled_gate_block(d, tiles, Cbuf, &fire_sh, defer ? my_row : -1, &rn_sh, shifted_meas(d.measurement));
   }
-  TRACE(0, 1)
   const int mode = !fire ? kSrcPrev : (d.resampler == NFDPF_RESAMPLE_SOFT ? kSrcSoft : kSrcOt);
   const RowSlot S = row_slot(d, b);
   const float *xprev = d.x_prev + b * d.x_prev_rs;
@@ -560,62 +520,16 @@ __global__ __launch_bounds__(kTile) void tiled_front_kernel(const nfdpf_filter_d
     const FoldRef r = fold_ref(d.cond_params, net_size<1, kH>(d.E + 4), threadIdx.x);
     ws.cb_cond[b * kCb + threadIdx.x] = fold_acc(r, d.E + 4, fold_bias0(r, d.E + 4), S.enc, 0, d.E);
   }
-  TRACE(0, 2)
   store_sums4(ws.st_phys + ((int64_t)b * tiles + tile) * 4, s0, s1, q0, q1, shd);
-  TRACE(0, 3)
 }
 
-// ---- the fused step (tiled_step_fused_kernel, below; opt-in, see use_fused): the merged front
-// launch and the quad proposal launch as ONE launch per step.  Their only coupling inside a step is the row's x_dyn
-// sums (the proposal's [mean, std] context): instead of a launch boundary, the four workgroups
-// of a row exchange their partials through data-tagged 8-byte granules {32 data bits, tag}
-// (agent-scope stores / loads: L2, no flag, no fence; MI355X_MICROARCH.md handoff-1to1).  The
-// tag is (pass epoch << 16) + t + 1 -- the epoch is bumped by a one-lane kernel at the start
-// of every pass (graph replays included), so granules of an earlier pass never match.  Needs
-// every workgroup of the grid resident at once (the host checks grid <= CUs, one 1024-thread
-// workgroup per CU); a poll that never sees its tag gives up at kSpinCap and counts a fault.
-__device__ uint32_t g_step_epoch = 0;
-constexpr int kFusedMaxTiles = kMergedMaxN_ / kTile;
-struct FusedLds {
-  float cb[kMaxFlows * 4 * kH];       // nf_dyn fold of the row (tiled_fdyn_kernel's cb, flat)
-  float encfold[kMaxFlows * 4 * kH];  // the proposal fold over the encoding columns
-  double rowst[kFusedMaxTiles * 4];   // the row's x_dyn partials, tile order (tiled_ctx input)
-};
-__device__ __forceinline__ void publish_granules(uint64_t *g, double v, uint32_t tag) {
-  const uint64_t bits = (uint64_t)__double_as_longlong(v);
-  __hip_atomic_store(g, ((uint64_t)tag << 32) | (bits & 0xffffffffull), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  __hip_atomic_store(g + 1, ((uint64_t)tag << 32) | (bits >> 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// wave 0 polls the row's granules (8 per tile) until every tag matches, then leaves the
-// doubles in fx->rowst; all threads call (one barrier)
-__device__ __forceinline__ void row_sync(const nfdpf_filter_desc &d, const TiledWs &ws, FusedLds *fx, uint32_t tag) {
-  const int tiles = n_tiles(d.N);
-  const int ng = tiles * 8;
-  if (threadIdx.x < 64) {
-    int b, tile;
-    tile_row(b, tile);
-    const uint64_t *g = ws.rowx + (int64_t)b * tiles * 8;
-    for (int base = 0; base < ng; base += 64) {
-      const int q = base + (int)threadIdx.x;
-      uint64_t v = 0;
-      bool ok = q >= ng;
-      for (int it = 0;; ++it) {
-        if (!ok) {
-          v = __hip_atomic_load(g + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          ok = (uint32_t)(v >> 32) == tag;
-        }
-        if (__all(ok)) break;
-        if (it >= kSpinCap) {
-          if (threadIdx.x == 0) atomicAdd(&g_split_fault, 1);
-          break;
-        }
-        __builtin_amdgcn_s_sleep(1);
-      }
-      if (q < ng) reinterpret_cast<uint32_t *>(fx->rowst)[q] = (uint32_t)v;
-    }
-  }
-  __syncthreads();
-}
+// (The fused step -- the merged front launch and the quad proposal launch as ONE launch per
+// step, a row's four workgroups exchanging their x_dyn partials through tagged granules instead
+// of a launch boundary -- was bit-identical and measured SLOWER at C2: 1.483 vs 1.471 ms per pass,
+// one box, profiles/r02_experiments.md.  The granule exchange itself cost ~0.8 us against the
+// 1.65 us launch gap it removed, but the front half ran 2.3 us longer inside the 16-wave workgroup
+// than as its own 8-wave launch, and the proposal half's prologue stayed at 2 us.  Retired;
+// f81620f is the last commit that holds it.)
 
 // ---- K2: nf_dyn inverse; with defer_norm also the normalisation of slot t-1 (finish_prev's
 // arithmetic, its sums reduced together with this launch's in one barrier).  SPLIT: the
@@ -624,12 +538,12 @@ __device__ __forceinline__ void row_sync(const nfdpf_filter_desc &d, const Tiled
 // Each role's waves reduce their own four sums; thread k < 8 adds the wave partials of role
 // k / 4 in particle-group order (waves k / 4, 2 + k / 4, ...) -- the order of block_sum8_store
 // over the same particles.
-__device__ __forceinline__ void block_sum_roles_store(const double (&v)[4], double *dst0, double *dst1,
-                                                      double *sh, uint64_t *gran = nullptr, uint32_t tag = 0) {
+__device__ __forceinline__ void block_sum_roles_store(const double (&v)[4], double *dst0, double *dst1, double *sh) {
   const int w = threadIdx.x >> 6;
   // a role whose destination is null skips its reductions (wave-uniform; fp64 DPP sums of 8
   // waves are a visible share of a short launch's epilogue)
-  if (w < 8 && (w & 1 ? dst1 : dst0) != nullptr) {  // waves >= 8 (the fused step's) hold nothing here
+  // (w < 8 always holds at 512 threads; dropping it changes the callers' register allocation)
+  if (w < 8 && (w & 1 ? dst1 : dst0) != nullptr) {
     double w4[4] = {v[0], v[1], v[2], v[3]};
     wave_sum_dpp_n(w4);
     if ((threadIdx.x & 63) == 0)
@@ -644,7 +558,6 @@ __device__ __forceinline__ void block_sum_roles_store(const double (&v)[4], doub
       double a = sh[4 * r + k];
       for (int q = 1; q < 4; ++q) a += sh[4 * (2 * q + r) + k];
       dst[k] = a;
-      if (gran && r == 0) publish_granules(gran + 2 * k, a, tag);  // the fused step's row exchange
     }
   }
 }
@@ -657,7 +570,6 @@ __global__ __launch_bounds__(SPLIT ? 2 * kTile : kTile) void tiled_dyn_kernel(co
   __shared__ f2 cbs[SPLIT ? kMaxFlows * 2 * kH : 1];  // split order (split_cb_index)
   __shared__ __attribute__((aligned(8))) float xbuf[SPLIT ? 8 * kTile : 1];
   __shared__ int xflag[16];
-  TRACE(1, 0)
   const int tiles = n_tiles(d.N);
   int b, tile;
   tile_row(b, tile);
@@ -692,7 +604,6 @@ __global__ __launch_bounds__(SPLIT ? 2 * kTile : kTile) void tiled_dyn_kernel(co
   __syncthreads();
   if (tile == 0 && threadIdx.x < d.n_flows * 4 * kH)  // K3's nf_dyn forward uses the same fold
     ws.cb_dyn[b * kCb + threadIdx.x] = reinterpret_cast<const float *>(cb)[threadIdx.x];
-  TRACE(1, 1)
   double sd[4] = {0, 0, 0, 0}, sf[4] = {0, 0, 0, 0};
   if (i < d.N) {
     float x0 = 0.f, x1 = 0.f;
@@ -720,7 +631,6 @@ __global__ __launch_bounds__(SPLIT ? 2 * kTile : kTile) void tiled_dyn_kernel(co
       sf[3] = lw;
     }
   }
-  TRACE(1, 2)
   double *dst = ws.st_dyn + ((int64_t)b * tiles + tile) * 4;
   double *dfin = defer ? ws.fin + (((int64_t)b * d.T + d.t - 1) * tiles + tile) * 4 : nullptr;
   if (SPLIT)
@@ -729,7 +639,6 @@ __global__ __launch_bounds__(SPLIT ? 2 * kTile : kTile) void tiled_dyn_kernel(co
     block_sum8_store(sd, dst, sf, dfin, shd);
   else
     store_sums4(dst, sd[0], sd[1], sd[2], sd[3], shd);
-  TRACE(1, 3)
 }
 
 // ---- K1+K2 merged (the split-net path of --NF-dyn RealNVP with --NF-cond and the cosine
@@ -743,9 +652,7 @@ __global__ __launch_bounds__(SPLIT ? 2 * kTile : kTile) void tiled_dyn_kernel(co
 // its deferred normalisation moves to the proposal launch (the scratch row is double-
 // buffered by step parity, so step t's propose / prior do not overwrite step t-1's).
 // Dynamic LDS: C[max(N, B_global)], w'[N], p_{t-1}[N].
-template <bool FUSED>
-__device__ __forceinline__ void fdyn_part(const nfdpf_filter_desc &d, const TiledWs &ws, FusedLds *fx,
-                                          uint32_t tag) {
+__device__ __forceinline__ void fdyn_part(const nfdpf_filter_desc &d, const TiledWs &ws) {
   extern __shared__ float dyn_lds[];
   __shared__ double shd[64];
   __shared__ float shf[16];
@@ -758,14 +665,13 @@ __device__ __forceinline__ void fdyn_part(const nfdpf_filter_desc &d, const Tile
   __shared__ f2 cbs[kMaxFlows * 2 * kH];
   __shared__ __attribute__((aligned(8))) float xbuf[8 * kTile];
   __shared__ int xflag[16];
-  TRACE(0, 0)
   const int tiles = n_tiles(d.N), N = d.N;
   int b, tile;
   tile_row(b, tile);
   const SplitLane sl = split_lane(8);
   const int role = sl.role, slot = sl.slot;
   const int i = tile * kTile + slot;
-  const bool valid = i < N && (!FUSED || role < 2);  // fused: waves 8-15 carry no particle here
+  const bool valid = i < N;
   const int64_t grow = d.row_base + b;
   const bool defer = d.defer_norm && d.t > 0;
   const bool shifted = shifted_meas(d.measurement);
@@ -816,13 +722,10 @@ __device__ __forceinline__ void fdyn_part(const nfdpf_filter_desc &d, const Tile
 #pragma unroll
     for (int c = 0; c < kOctxDyn; ++c) fw[1 + c] = r.w1c[2 * (r.j * kOctxDyn + c) + r.w];
   }
-  // fused: every workgroup folds for itself, on the otherwise idle waves 8-15
-  const int enc_fold_t0 = FUSED ? 2 * kTile : kTile;
-  const bool enc_fold_lane = d.nf_cond && (FUSED || tile == 0) && threadIdx.x >= enc_fold_t0 &&
-                             threadIdx.x - enc_fold_t0 < d.n_flows * 4 * kH;
+  const bool enc_fold_lane = d.nf_cond && tile == 0 && threadIdx.x >= kTile && threadIdx.x - kTile < d.n_flows * 4 * kH;
   float enc_fold = 0.f;
   if (enc_fold_lane) {  // proposal fold over the encoding columns (model/models.py:338-346); K3 adds mean/std
-    const FoldRef r = fold_ref(d.cond_params, net_size<1, kH>(d.E + 4), threadIdx.x - enc_fold_t0);
+    const FoldRef r = fold_ref(d.cond_params, net_size<1, kH>(d.E + 4), threadIdx.x - kTile);
     enc_fold = fold_acc_pipe(r, d.E + 4, fold_bias0(r, d.E + 4), S.enc, 0, d.E);
   }
   // the row's sums over x_phys = (x_src + vel) + eps (motion_apply_eps's arithmetic)
@@ -874,17 +777,15 @@ __device__ __forceinline__ void fdyn_part(const nfdpf_filter_desc &d, const Tile
       }
       __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): this wave's LDS writes have landed
       __builtin_amdgcn_wave_barrier();
-      TRACEW(0, 4)
       const float s = cascade_row_sum([&](int r) { return Cbuf[r]; }, d.B_global);
       if (threadIdx.x == 0) fire_sh = (s / (float)d.B_global) < 0.5f * (float)N;
-      TRACEW(0, 5)
     }
-  } else if (spec && (!FUSED || threadIdx.x < 2 * kTile)) {
+  } else if (spec) {
     // every source load of this thread first (one memory latency instead of one per
     // particle), then the draws and sums; N <= kMergedMaxN = 4096 -> <= 10 per thread
     constexpr int kPer = 10;
     const float *src = defer ? Sp.hx : xprev;
-    const int j0 = threadIdx.x - 64, js = 2 * kTile - 64;  // waves 1-7 (fused too: the same sums)
+    const int j0 = threadIdx.x - 64, js = 2 * kTile - 64;  // waves 1-7
     float xs0[kPer], xs1[kPer];
 #pragma unroll
     for (int k = 0; k < kPer; ++k) {
@@ -901,26 +802,16 @@ __device__ __forceinline__ void fdyn_part(const nfdpf_filter_desc &d, const Tile
       if (j < N) motion_noise(d, b, grow, j, n0[k], n1[k]);
     }
     if (valid) motion_noise(d, b, grow, i, e0, e1);
-#ifdef NFDPF_EXP_TRACE
-    if (threadIdx.x >> 6 == 1) {  // wave 1: draws done / its source loads landed
-      TRACEW(0, 6)
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-#endif
 #pragma unroll
     for (int k = 0; k < kPer; ++k) {
       const int j = j0 + k * js;
       if (j < N) acc_n(xs0[k], xs1[k], n0[k], n1[k]);
     }
-#ifdef NFDPF_EXP_TRACE
-    if (threadIdx.x >> 6 == 1) TRACEW(0, 7)
-#endif
   } else if (valid) {
     motion_noise(d, b, grow, i, e0, e1);
   }
   __syncthreads();
   const bool fire = fire_sh != 0;
-  TRACE(0, 1)
   const int mode = !fire ? kSrcPrev : (d.resampler == NFDPF_RESAMPLE_SOFT ? kSrcSoft : kSrcOt);
   const RowNorm rn = defer ? rn_sh : RowNorm{0.f, 1.f, 0.f};
   auto prev_p = [&](int j) {
@@ -1004,8 +895,7 @@ __device__ __forceinline__ void fdyn_part(const nfdpf_filter_desc &d, const Tile
   {
     double w4[4] = {a0, a1, c0, c1};
     const int w = threadIdx.x >> 6;
-    // the fused step's waves 8-15 accumulated nothing unless they resampled: zeros, no DPP
-    if (!FUSED || w < 8 || mode != kSrcPrev || !spec) wave_sum_dpp_n(w4);
+    wave_sum_dpp_n(w4);
     if ((threadIdx.x & 63) == 0)
 #pragma unroll
       for (int k = 0; k < 4; ++k) shd[4 * w + k] = w4[k];
@@ -1029,18 +919,11 @@ __device__ __forceinline__ void fdyn_part(const nfdpf_filter_desc &d, const Tile
     for (int q = 0; q < kOctxDyn; ++q) v = fmaf(fw[1 + q], cv[q], v);
     reinterpret_cast<float *>(cb)[threadIdx.x] = v;
     reinterpret_cast<float *>(cbs)[split_cb_index(threadIdx.x)] = v;
-    if (FUSED) fx->cb[threadIdx.x] = v;
   }
-  if (enc_fold_lane) {
-    if (FUSED)
-      fx->encfold[threadIdx.x - enc_fold_t0] = enc_fold;
-    else
-      ws.cb_cond[b * kCb + threadIdx.x - kTile] = enc_fold;
-  }
+  if (enc_fold_lane) ws.cb_cond[b * kCb + threadIdx.x - kTile] = enc_fold;
   __syncthreads();
-  if (!FUSED && tile == 0 && threadIdx.x < d.n_flows * 4 * kH)  // K3's nf_dyn forward uses the same fold
+  if (tile == 0 && threadIdx.x < d.n_flows * 4 * kH)  // K3's nf_dyn forward uses the same fold
     ws.cb_dyn[b * kCb + threadIdx.x] = reinterpret_cast<const float *>(cb)[threadIdx.x];
-  TRACE(0, 2)
   double sd[4] = {0, 0, 0, 0};
   if (valid) {
     float p0, p1;
@@ -1061,13 +944,14 @@ __device__ __forceinline__ void fdyn_part(const nfdpf_filter_desc &d, const Tile
       sd[3] = (double)xd1 * xd1;
     }
   }
-  block_sum_roles_store(sd, ws.st_dyn + ((int64_t)b * tiles + tile) * 4, nullptr, shd,
-                        FUSED ? ws.rowx + ((int64_t)b * tiles + tile) * 8 : nullptr, tag);
-  TRACE(0, 3)
+  block_sum_roles_store(sd, ws.st_dyn + ((int64_t)b * tiles + tile) * 4, nullptr, shd);
 }
 
+// (fdyn_part and quad_part stay functions inlined into their one kernel: written as the kernel's
+// own body, tiled_fdyn_kernel compiles to another register allocation -- 95 instead of 137 VGPRs --
+// and schedule, which nobody has measured)
 __global__ __launch_bounds__(2 * kTile) void tiled_fdyn_kernel(const nfdpf_filter_desc d, TiledWs ws) {
-  fdyn_part<false>(d, ws, nullptr, 0u);
+  fdyn_part(d, ws);
 }
 
 // softmax partials of the unshifted log-weight u over this tile
@@ -1188,23 +1072,20 @@ __device__ __forceinline__ void store_softmax_fin(float u, bool valid, double *s
 }
 
 // ---- K3: proposal + measurement
-// STAGE (CRNVP, use_stage, opt-in): the measurement's encoder and flow weights copied into LDS
-// once per workgroup and read from there (ds_read) instead of streamed through the scalar cache
-// (26 KB, more than it holds).  Measured slower: not the default.
-// MV (CRNVP): 0 = the measurement per lane with its weights through the scalar cache, 1 = the
-// same with the weights staged in LDS (STAGE), 2 = on f32 MFMA, 64 particles per wave with the
-// fragment blob (d.meas_mfma, csrc/crnvp_mfma.hpp) staged in LDS -- the step launch of the C3
-// shape when a gate fires (the no-flow pass reruns step by step with the Sinkhorn)
-constexpr int kCrnvpPe = pe_size(kE);                                  // encoder floats
-constexpr int kCrnvpFlow = 2 * 2 * net_size<kE / 2, kH>(kE);           // floats per flow
-template <bool NFD, bool NFC, int MEAS, int MV = 0>
+// MF (CRNVP, d.meas_mfma): the measurement on f32 MFMA, 64 particles per wave with the fragment
+// blob (csrc/crnvp_mfma.hpp) staged in LDS -- the step launch of the C3 shape when a gate fires
+// (the no-flow pass reruns step by step with the Sinkhorn); otherwise the measurement per lane
+// with its weights through the scalar cache.
+// (The per-lane measurement with its encoder and flow weights staged in LDS, 26 KB and more than
+// the scalar cache holds, measured SLOWER than the scalar-cache stream at C3: 48 vs 31 us per
+// launch, 1.11e9 vs 1.58e9 -- one ds_read_b128 per two v_pk_fma, 254 VGPRs leave the compiler two
+// or three reads in flight.  Retired; f81620f is the last commit that holds it.)
+template <bool NFD, bool NFC, int MEAS, bool MF = false>
 __global__ __launch_bounds__(kTile) void tiled_prop_kernel(const nfdpf_filter_desc d, TiledWs ws) {
-  constexpr bool STAGE = MV == 1, MF = MV == 2;
   static_assert(!MF || (MEAS == NFDPF_MEAS_CRNVP && !NFC), "MFMA measurement: CRNVP, bootstrap or nf_dyn proposal");
   __shared__ StepShared L;
-  extern __shared__ float4 wstage[];  // STAGE: [encoder | flows] weights; MF: the fragment blob
+  extern __shared__ float4 wstage[];  // MF: the fragment blob
   __shared__ float xw[MF ? kTile : 1][2];  // MF: the proposals, per wave, for its MFMA measurement
-  TRACE(2, 0)
   const int tiles = n_tiles(d.N);
   int b, tile;
   tile_row(b, tile);
@@ -1213,13 +1094,6 @@ __global__ __launch_bounds__(kTile) void tiled_prop_kernel(const nfdpf_filter_de
   const bool valid = i < d.N;
   PropIn in{};
   float lr = 0.f;
-  if constexpr (STAGE) {  // 16-B aligned blobs, whole float4s (checked on the host)
-    const float4 *pe4 = reinterpret_cast<const float4 *>(d.pe_params);
-    const float4 *mp4 = reinterpret_cast<const float4 *>(d.meas_params);
-    const int nmp4 = d.n_flows * kCrnvpFlow / 4;
-    for (int k = threadIdx.x; k < kCrnvpPe / 4; k += kTile) wstage[k] = pe4[k];
-    for (int k = threadIdx.x; k < nmp4; k += kTile) wstage[kCrnvpPe / 4 + k] = mp4[k];
-  }
   if constexpr (MF) {  // 16-B aligned blob of whole float4s (checked on the host)
     const float4 *mp4 = reinterpret_cast<const float4 *>(d.meas_params);
     for (int k = threadIdx.x; k < crnvp_mfma_floats(d.n_flows) / 4; k += kTile) wstage[k] = mp4[k];
@@ -1243,7 +1117,6 @@ __global__ __launch_bounds__(kTile) void tiled_prop_kernel(const nfdpf_filter_de
   __syncthreads();
   if (!NFD && d.defer_norm && d.t > 0)  // no K2 in this config
     finish_prev(d, ws, b, tile, i, true, i < d.N ? load_prev_in(row_slot(d, b, d.t - 1), i) : PrevIn{}, L.d);
-  TRACE(2, 1)
   float lk = -INFINITY, u = 0.f, propose = 0.f, prior = 0.f;
   if constexpr (MF) {  // the proposal per lane, then the wave's 64 likelihoods on MFMA
     float q0x = 0.f, q1x = 0.f;
@@ -1264,21 +1137,12 @@ __global__ __launch_bounds__(kTile) void tiled_prop_kernel(const nfdpf_filter_de
     }
   } else if (valid) {
     float q0x, q1x;
-    if constexpr (STAGE) {
-      static_assert(!STAGE || MEAS == NFDPF_MEAS_CRNVP, "staged weights: CRNVP only");
-      const float jp = stage_propose_inverse<NFC>(d, in, L.cb_cond, q0x, q1x);
-      stage_prior<NFD, NFC>(d, S, i, in, L.cb_dyn, q0x, q1x, jp, propose, prior);
-      const float *wl = reinterpret_cast<const float *>(wstage);
-      lk = crnvp_lik(wl, wl + kCrnvpPe, d.n_flows, d.meas_prior_std, L.encv, q0x, q1x);
-    } else {
-      lk = stage_proposal<NFD, NFC, MEAS>(d, S, L, i, in, L.cb_dyn, L.cb_cond, q0x, q1x, propose, prior);
-    }
+    lk = stage_proposal<NFD, NFC, MEAS>(d, S, L, i, in, L.cb_dyn, L.cb_cond, q0x, q1x, propose, prior);
     if (MEAS != NFDPF_MEAS_EXTERNAL) {
       S.hlik[i] = lk;
       u = logw(lr, lk, prior, propose);
     }
   }
-  TRACE(2, 2)
   if (MEAS == NFDPF_MEAS_EXTERNAL) return;  // phase 1: the external likelihood comes next
   double *sm = reinterpret_cast<double *>(d.ess_out) + ((int64_t)b * tiles + tile) * kSm;
   __shared__ double smd[48];
@@ -1291,7 +1155,6 @@ __global__ __launch_bounds__(kTile) void tiled_prop_kernel(const nfdpf_filter_de
     if (threadIdx.x == 0) sm[3] = lm;
     store_softmax(u, valid, sm, L.f + 8, smd);  // L.f[0:8] held block_max
   }
-  TRACE(2, 3)
 }
 
 // ---- K3, two roles: 512 threads for a tile of 256 particles.  Waves 0-3 ("flows") run the
@@ -1309,7 +1172,6 @@ __global__ __launch_bounds__(ROLES * kTile) void tiled_prop2_kernel(const nfdpf_
   __shared__ double ssx[ROLES][kTile], dotx[ROLES][kTile];
   __shared__ float smf[16];   // per-wave softmax partials (up to 12 waves)
   __shared__ double smd[48];
-  TRACE(2, 0)
   const int tiles = n_tiles(d.N);
   int b, tile;
   tile_row(b, tile);
@@ -1340,7 +1202,6 @@ __global__ __launch_bounds__(ROLES * kTile) void tiled_prop2_kernel(const nfdpf_
   if (!NFD && d.defer_norm && d.t > 0)  // no K2 in this config
     finish_prev(d, ws, b, tile, i, flows, flows && i < d.N ? load_prev_in(row_slot(d, b, d.t - 1), i) : PrevIn{},
                 L.d);
-  TRACE(2, 1)
   float q0x = 0.f, q1x = 0.f, jp = 0.f;
   if (flows && valid) {
     jp = stage_propose_inverse<NFC>(d, in, L.cb_cond, q0x, q1x);
@@ -1348,7 +1209,6 @@ __global__ __launch_bounds__(ROLES * kTile) void tiled_prop2_kernel(const nfdpf_
     qx[pl][1] = q1x;
   }
   __syncthreads();
-  TRACE(2, 4)
   float lk = -INFINITY, u = 0.f, propose = 0.f, prior = 0.f;
   const int role = threadIdx.x / kTile;
   if (valid) {
@@ -1379,143 +1239,24 @@ __global__ __launch_bounds__(ROLES * kTile) void tiled_prop2_kernel(const nfdpf_
     }
     u = logw(lr, lik, prior, propose);
   }
-  TRACE(2, 2)
   double *sm = reinterpret_cast<double *>(d.ess_out) + ((int64_t)b * tiles + tile) * kSm;
   // the measurement waves hold lk, the others -inf
   const float lm = meas_shifted<MEAS>() ? block_max_dpp(lk, L.f) : 0.f;
   if (threadIdx.x == 0) sm[3] = lm;
   store_softmax(u, valid && flows, sm, smf, smd);
-  TRACE(2, 3)
 }
 
-// ---- K3 for the conditional-RealNVP measurement without an NF proposal (C3, DPF-CM): 512
-// threads per tile of 256 particles.  The measurement's flow input is the row's frame encoding
-// and its condition the particle encoding (model/models.py:256-278), so a particle's work is two
-// chains: waves 4-7 ("cond") encode the proposal and fold the encoding into every coupling
-// half's first-layer bias pairs (the context columns of nf/flows.py:215-226's nets), publishing
-// them half by half through LDS; waves 0-3 ("flow", the same particles as cond wave w + 4) take
-// the densities while the encoder runs, then the coupling nets on the frame encoding as each
-// half's biases arrive.  Two waves per SIMD instead of one at C3's 64 000 particles: one chain's
-// scalar-load stalls are the other's issue slots.  The arithmetic is measure<CRNVP>'s, split at
-// the fold (bit-identical).  Not the default: measured slower (use_cm).
-static __host__ __device__ constexpr size_t cm_lds_bytes(int n_flows) {
-  return (size_t)2 * n_flows * kH * kTile * sizeof(f2);
-}
-template <bool NFD>
-__global__ __launch_bounds__(2 * kTile) void tiled_prop_cm_kernel(const nfdpf_filter_desc d, TiledWs ws) {
-  extern __shared__ f2 cbx[];  // [half h = 2 flow + n][kH][kTile] folded bias pairs
-  __shared__ StepShared L;
-  __shared__ int cflag[4];     // halves published by cond wave w + 4 (for flow wave w)
-  __shared__ float smf[16];
-  __shared__ double smd[48];
-  TRACE(2, 0)
-  constexpr int HALF = kE / 2;
-  constexpr int ns = net_size<HALF, kH>(kE);
-  const int tiles = n_tiles(d.N);
-  int b, tile;
-  tile_row(b, tile);
-  const int pl = threadIdx.x & (kTile - 1);
-  const bool flows = threadIdx.x < kTile;
-  const int i = tile * kTile + pl;
-  const RowSlot S = row_slot(d, b);
-  const bool valid = i < d.N;
-  PropIn in{};
-  float lr = 0.f;
-  if (valid) {  // issued before the row prologue so they overlap it
-    if (flows) {
-      in = load_prop_in<NFD>(S, i);
-      lr = S.hp[i];
-    } else {  // the proposal (= x_dyn without --NF-cond, stage_propose_inverse)
-      in.xd0 = NFD ? S.scr[4 * i] : S.hx[2 * i];
-      in.xd1 = NFD ? S.scr[4 * i + 1] : S.hx[2 * i + 1];
-    }
-  }
-  measure_row_setup<NFDPF_MEAS_CRNVP>(S.enc, d.meas_params, L);
-  if (threadIdx.x < 4) cflag[threadIdx.x] = 0;
-  __syncthreads();
-  if (!NFD && d.defer_norm && d.t > 0)  // no K2 in this config
-    finish_prev(d, ws, b, tile, i, flows, flows && i < d.N ? load_prev_in(row_slot(d, b, d.t - 1), i) : PrevIn{},
-                L.d);
-  TRACE(2, 1)
-  const int nh = 2 * d.n_flows;
-  lds_vint *flag = (lds_vint *)&cflag[__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) & 3];
-  float lk = -INFINITY, u = 0.f, propose = 0.f, prior = 0.f;
-  if (!flows) {
-    float e[kE];
-    particle_encode<kE>(wptr(d.pe_params), in.xd0, in.xd1, e);
-    for (int h = 0; h < nh; ++h) {
-      cf2 *fw = wptr2(d.meas_params) + h * ns;  // flow h / 2, coupling half h % 2
-#pragma unroll
-      for (int j = 0; j < kH; ++j) cbx[(h * kH + j) * kTile + pl] = fold_pair_c<HALF, kH, kE>(fw, j, e);
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the pairs land before the count
-      *flag = h + 1;
-    }
-  } else {
-    if (valid) stage_prior<NFD, false>(d, S, i, in, nullptr, in.xd0, in.xd1, 0.f, propose, prior);
-    float lo[HALF], up[HALF];
-#pragma unroll
-    for (int k = 0; k < HALF; ++k) {
-      lo[k] = L.encv[k];
-      up[k] = L.encv[HALF + k];
-    }
-    float ld = 0.f;
-    for (int f = 0; f < d.n_flows; ++f) {
-      cf2 *fw = wptr2(d.meas_params) + f * 2 * ns;
-      f2 cb[kH];
-      float t[HALF], s[HALF];
-      // coupling_forward, half by half as the cond wave publishes the bias pairs
-      int it = 0;
-      for (; __builtin_amdgcn_readfirstlane(*flag) < 2 * f + 1 && it < kSpinCap; ++it) __builtin_amdgcn_s_sleep(1);
-      if (it == kSpinCap && (threadIdx.x & 63) == 0) atomicAdd(&g_split_fault, 1);
-      asm volatile("" ::: "memory");
-#pragma unroll
-      for (int j = 0; j < kH; ++j) cb[j] = cbx[(2 * f * kH + j) * kTile + pl];
-      ts_pair<HALF, kH>(fw, lo, cb, t, s);
-#pragma unroll
-      for (int k = 0; k < HALF; ++k) up[k] = t[k] + up[k] * expf(s[k]);
-      const float l1 = half_sum<HALF>(s);
-      it = 0;
-      for (; __builtin_amdgcn_readfirstlane(*flag) < 2 * f + 2 && it < kSpinCap; ++it) __builtin_amdgcn_s_sleep(1);
-      if (it == kSpinCap && (threadIdx.x & 63) == 0) atomicAdd(&g_split_fault, 1);
-      asm volatile("" ::: "memory");
-#pragma unroll
-      for (int j = 0; j < kH; ++j) cb[j] = cbx[((2 * f + 1) * kH + j) * kTile + pl];
-      ts_pair<HALF, kH>(fw + ns, up, cb, t, s);
-#pragma unroll
-      for (int k = 0; k < HALF; ++k) lo[k] = t[k] + lo[k] * expf(s[k]);
-      ld += l1 + half_sum<HALF>(s);
-    }
-    // the prior's quadratic form in fp64, as measure<CRNVP>
-    const double is = 1.0 / (double)d.meas_prior_std;
-    double m = 0.0;
-#pragma unroll
-    for (int k = 0; k < HALF; ++k) {
-      const double a = lo[k] * is, c = up[k] * is;
-      m = fma(a, a, m);
-      m = fma(c, c, m);
-    }
-    const double lp = -0.5 * (kE * 1.8378770664093453 + m) - kE * log((double)d.meas_prior_std);
-    if (valid) {
-      lk = (float)(lp + (double)ld);
-      S.hlik[i] = lk;
-      u = logw(lr, lk, prior, propose);
-    }
-  }
-  TRACE(2, 2)
-  double *sm = reinterpret_cast<double *>(d.ess_out) + ((int64_t)b * tiles + tile) * kSm;
-  // the log-weight relative to the wave's max raw likelihood (tiled_prop_kernel's); the cond waves hold -inf
-  const float lmw = wave_max_dpp(lk);
-  if (valid && flows) u = logw(lr, lk - lmw, prior, propose);
-  store_softmax_rel(u, valid && flows, lmw, sm, smf, smd);
-  TRACE(2, 3)
-}
+// (A two-chain CRNVP proposal launch for C3 -- 512 threads per tile, waves 4-7 encoding the
+// proposal and folding the encoding into every coupling half's bias pairs while waves 0-3 took
+// the densities and then the coupling nets, two waves per SIMD instead of one -- was bit-identical
+// and measured SLOWER than the one-chain tiled_prop_kernel at C3: 33.7 vs 30.7 us per launch,
+// 1.455e9 vs 1.566e9 particle-steps/s, one box.  Retired; f81620f is the last commit that holds it.)
 
 // ---- K3 on wave pairs (split.hpp; --NF-dyn RealNVP, --NF-cond, cosine measurement): the
 // t-wave and the s-wave of a particle group run the proposal inverse and the nf_dyn forward
 // net by net, then split the particle encoder's output layer (each computes the hidden
 // layers, then half of the 32 outputs) and exchange their partial |e|^2 and <e, v>.  No
 // wave idles and no workgroup barrier separates the stages.  512 threads per tile.
-template <bool MERGED>
 __global__ __launch_bounds__(2 * kTile) void tiled_prop_split_kernel(const nfdpf_filter_desc d, TiledWs ws) {
   __shared__ StepShared L;  // cb_dyn / cb_cond in split order
   __shared__ __attribute__((aligned(8))) float xbuf[8 * kTile];
@@ -1524,7 +1265,6 @@ __global__ __launch_bounds__(2 * kTile) void tiled_prop_split_kernel(const nfdpf
   __shared__ int xflag[16];
   __shared__ float smf[16];
   __shared__ double smd[48];
-  TRACE(2, 0)
   const int tiles = n_tiles(d.N);
   int b, tile;
   tile_row(b, tile);
@@ -1535,18 +1275,10 @@ __global__ __launch_bounds__(2 * kTile) void tiled_prop_split_kernel(const nfdpf
   const bool valid = i < d.N;
   PropIn in{};
   float lr = 0.f;
-  // with the merged front + dyn launch, slot t-1's deferred normalisation runs here (role 1)
-  const bool defer_here = MERGED && d.defer_norm && d.t > 0 && role == 1;
-  PrevIn pv{};
   if (valid) {  // issued before the row prologue so they overlap it
     in = load_prop_in<true>(S, i);
     if (role == 0) lr = S.hp[i];
-    if (defer_here) pv = load_prev_in(row_slot(d, b, d.t - 1), i);
   }
-  // slot t-1's row normaliser (softmax partials of the previous launch): read now, so its
-  // global latency hides under the prologue instead of the epilogue
-  const RowNorm rn_prev = defer_here && valid ? row_norm(prev_sm(d, b, tiles), tiles, shifted_meas(d.measurement))
-                                              : RowNorm{0.f, 1.f, 0.f};
   measure_row_setup<NFDPF_MEAS_COS>(S.enc, d.meas_params, L);
   if (threadIdx.x < 16) xflag[threadIdx.x] = 0;
   pair_clear(xbuf, kTile);
@@ -1563,7 +1295,6 @@ __global__ __launch_bounds__(2 * kTile) void tiled_prop_split_kernel(const nfdpf
         fold_acc(r, d.E + 4, ws.cb_cond[b * kCb + k], c4, d.E, d.E + 4);
   }
   __syncthreads();
-  TRACE(2, 1)
   PairX x = pair_of(xbuf, xflag, role, slot);
   float u = 0.f;
   if (valid) {
@@ -1573,12 +1304,8 @@ __global__ __launch_bounds__(2 * kTile) void tiled_prop_split_kernel(const nfdpf
     // cosine measurement (model/models.py:206-219): outputs [16 role, 16 role + 16) here
     double ss, dot;
     double ss_o, dot_o;
-#ifdef NFDPF_EXP_NOENC  // experiment builds only: the cosine encoder left out (prices it)
-    ss = 1.0 + q0x * 1e-9, dot = 0.5 + q1x * 1e-9, ss_o = 1.0, dot_o = 0.25;
-#else
     encode_dot_pair<kE>(wptr(d.pe_params), q0x, q1x, L.encv, ss, dot, x, hbuf, kTile);
     pair_swap_once2(x, ss, dot, dbuf, kTile, ss_o, dot_o);
-#endif
     ss = role ? ss_o + ss : ss + ss_o;
     dot = role ? dot_o + dot : dot + dot_o;
     const float lk = cos_lik(ss, dot, L.vinv);
@@ -1587,31 +1314,9 @@ __global__ __launch_bounds__(2 * kTile) void tiled_prop_split_kernel(const nfdpf
       u = logw(lr, lk, prior, propose);
     }
   }
-  TRACE(2, 2)
   double *sm = reinterpret_cast<double *>(d.ess_out) + ((int64_t)b * tiles + tile) * kSm;
   if (threadIdx.x == 0) sm[3] = 0.f;
-  if (MERGED && d.defer_norm && d.t > 0) {
-    // finish_prev's arithmetic for slot t-1 on role 1; its four sums and this step's softmax
-    // partials share one barrier
-    double sf[4] = {0, 0, 0, 0};
-    if (defer_here && valid) {
-      const bool shifted = shifted_meas(d.measurement);
-      const RowSlot Sp = row_slot(d, b, d.t - 1);
-      float lw, lk;
-      const float p = prev_p_of(pv, rn_prev, shifted, lw, lk);
-      if (shifted) Sp.hlik[i] = lk;
-      Sp.hp[i] = p;
-      sf[0] = (double)p * p;
-      sf[1] = (double)p * pv.x0;
-      sf[2] = (double)p * pv.x1;
-      sf[3] = lw;
-    }
-    store_softmax_fin(u, valid && role == 0, sm, sf, ws.fin + (((int64_t)b * d.T + d.t - 1) * tiles + tile) * 4,
-                      smf, smd);
-  } else {
-    store_softmax(u, valid && role == 0, sm, smf, smd);
-  }
-  TRACE(2, 3)
+  store_softmax(u, valid && role == 0, sm, smf, smd);
 }
 
 // The quad launch's softmax / deferred-normalisation partials: the encoder t-waves 8, 10, 12,
@@ -1671,16 +1376,11 @@ __device__ __forceinline__ void merge_partials_quad(double *sm, double *fin, con
 // runs BESIDE the nf_dyn forward: the launch costs proposal + max(nf_dyn forward, encoder)
 // instead of their sum, at four waves per SIMD.  While it waits for the proposal the encoder
 // t-wave normalises slot t-1's particles (the deferred normalisation).  1024 threads per tile.
-template <bool MERGED, bool FUSED>
-__device__ __forceinline__ void quad_part(const nfdpf_filter_desc &d, const TiledWs &ws, const FusedLds *fx) {
+template <bool MERGED>
+__device__ __forceinline__ void quad_part(const nfdpf_filter_desc &d, const TiledWs &ws) {
   __shared__ StepShared L;
   __shared__ __attribute__((aligned(8))) float xbuf[8 * kTile];              // flow-pair hand-offs (pair_swap)
-#ifdef NFDPF_ENC_VALU
-  __shared__ float hbuf[2 * kPeH2 / 2 * kTile];  // encoder hidden halves (encode_dot_pair)
-  __shared__ float dbuf[2 * 4 * kTile];          // fp64 cosine partials (pair_swap_once2)
-#else
   __shared__ float Hws[8][32 * kHPitch];         // each encoder wave's layer-2 / layer-3 outputs
-#endif
   __shared__ float qbuf[2 * kTile];              // the proposal, flow t-wave -> encoder pair
   __shared__ float rbuf[3 * kTile];              // likelihood | prior | propose per particle
   __shared__ float encq[8][kE];                  // each encoder wave's copy of the frame encoding
@@ -1689,8 +1389,6 @@ __device__ __forceinline__ void quad_part(const nfdpf_filter_desc &d, const Tile
   __shared__ int rflag[4];
   __shared__ float smf[16];
   __shared__ double smd[96];
-  TRACE(2, 0)
-  QTRACE(0)
   const int tiles = n_tiles(d.N);
   int b, tile;
   tile_row(b, tile);
@@ -1706,16 +1404,11 @@ __device__ __forceinline__ void quad_part(const nfdpf_filter_desc &d, const Tile
   // with the merged front + dyn launch, slot t-1's deferred normalisation runs here (encoder t-wave)
   const bool defer_here = MERGED && d.defer_norm && d.t > 0 && enc && role == 0;
   PrevIn pv{};
-#ifndef NFDPF_ENC_VALU
   EncFrag2 ef{};
   if (enc) ef = enc_frag2_load(d.pe_params);  // the encoder's weight fragments, once
   // an encoder wave's measured particles: lanes 0-31 <- particles [32 role, 32 role + 32) of the group
   const int slot_e = g * 64 + 32 * role + (threadIdx.x & 31), i_e = tile * kTile + slot_e;
   const bool valid_e = enc && (threadIdx.x & 63) < 32 && i_e < d.N;
-#else
-  const int slot_e = slot, i_e = i;
-  const bool valid_e = enc && role == 0 && valid;
-#endif
   if (valid) {  // issued before the row prologue so they overlap it
     if (!enc) in = load_prop_in<true>(S, i);
     if (defer_here) pv = load_prev_in(row_slot(d, b, d.t - 1), i);
@@ -1729,20 +1422,17 @@ __device__ __forceinline__ void quad_part(const nfdpf_filter_desc &d, const Tile
   if (threadIdx.x >= 4 && threadIdx.x < 8) rflag[threadIdx.x - 4] = 0;
   const int ncb = d.n_flows * 4 * kH;
   if (threadIdx.x < ncb)
-    reinterpret_cast<float *>(L.cb_dyn)[split_cb_index(threadIdx.x)] =
-        FUSED ? fx->cb[threadIdx.x] : ws.cb_dyn[b * kCb + threadIdx.x];
+    reinterpret_cast<float *>(L.cb_dyn)[split_cb_index(threadIdx.x)] = ws.cb_dyn[b * kCb + threadIdx.x];
   if (threadIdx.x >= kTile && threadIdx.x - kTile < ncb) {
     // finish the proposal fold: the encoding columns came from K1, add [mean, std] of x_dyn
     const int k = threadIdx.x - kTile;
-    const Ctx4 cp = FUSED ? tiled_ctx(fx->rowst, 0, tiles, d.N) : tiled_ctx(ws.st_dyn, b, tiles, d.N);
+    const Ctx4 cp = tiled_ctx(ws.st_dyn, b, tiles, d.N);
     const float c4[4] = {cp.m0, cp.m1, cp.s0, cp.s1};
     const FoldRef r = fold_ref(d.cond_params, net_size<1, kH>(d.E + 4), k);
     reinterpret_cast<float *>(L.cb_cond)[split_cb_index(k)] =
-        fold_acc(r, d.E + 4, FUSED ? fx->encfold[k] : ws.cb_cond[b * kCb + k], c4, d.E, d.E + 4);
+        fold_acc(r, d.E + 4, ws.cb_cond[b * kCb + k], c4, d.E, d.E + 4);
   }
   __syncthreads();
-  TRACE(2, 1)
-  QTRACE(1)
   double sf[4] = {0, 0, 0, 0};
   float u = 0.f;
   lds_vint *qf = (lds_vint *)(qflag + g), *rf = (lds_vint *)(rflag + g);
@@ -1760,7 +1450,6 @@ __device__ __forceinline__ void quad_part(const nfdpf_filter_desc &d, const Tile
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       *qf = 1;
     }
-    QTRACE(2)
     if (valid) {
       float propose, prior;
       stage_prior_split(d, S, i, in, L.cb_dyn, q0x, q1x, jp, x, kTile, propose, prior);
@@ -1773,7 +1462,6 @@ __device__ __forceinline__ void quad_part(const nfdpf_filter_desc &d, const Tile
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       *rf = 1;
     }
-    QTRACE(3)
   } else {
     // measure_row_setup (cosine), per encoder wave into its own LDS copy (no barrier needed)
     const int lane = threadIdx.x & 63;
@@ -1803,20 +1491,9 @@ __device__ __forceinline__ void quad_part(const nfdpf_filter_desc &d, const Tile
       for (; __builtin_amdgcn_readfirstlane(*qf) == 0 && it < kSpinCap; ++it) __builtin_amdgcn_s_sleep(1);
       if (it == kSpinCap && (threadIdx.x & 63) == 0) atomicAdd(&g_split_fault, 1);
       asm volatile("" ::: "memory");
-      QTRACE(2)
       // cosine measurement (model/models.py:206-219)
       double ss, dot;
-#ifdef NFDPF_ENC_VALU  // the pair splits the outputs: [16 role, 16 role + 16) here, then exchanges
-      PairX xe = pair_of(xbuf, xflag, role, slot);  // flags 8..15: the encoder pairs' own
-      double ss_o, dot_o;
-      encode_dot_pair<kE>(wptr(d.pe_params), qbuf[slot], qbuf[kTile + slot], encv, ss, dot, xe, hbuf, kTile);
-      pair_swap_once2(xe, ss, dot, dbuf, kTile, ss_o, dot_o);
-      ss = role ? ss_o + ss : ss + ss_o;
-      dot = role ? dot_o + dot : dot + dot_o;
-#else  // the pair splits the particles: no hand-off
       encode_dot_mfma_half<kE>(ef, role, qbuf + g * 64, qbuf + kTile + g * 64, encv, ss, dot, Hws[w - 8]);
-#endif
-      QTRACE(11)
       const float lk = cos_lik(ss, dot, vinv);
       if (valid_e) {
         S.hlik[i_e] = lk;
@@ -1828,41 +1505,19 @@ __device__ __forceinline__ void quad_part(const nfdpf_filter_desc &d, const Tile
         u = logw(lr, lk, rbuf[kTile + slot_e], rbuf[2 * kTile + slot_e]);
       }
     }
-    QTRACE(3)
   }
   // the encoder waves' softmax and slot t-1 partials, then the launch's one closing barrier
-#ifdef NFDPF_ENC_VALU
-  wave_partials_quad(u, valid_e, enc && role == 0, sf, smf, smd);
-#else
   wave_partials_quad(u, valid_e, enc, sf, smf, smd);
-#endif
   __syncthreads();
-  TRACE(2, 2)
-  QTRACE(4)
   double *sm = reinterpret_cast<double *>(d.ess_out) + ((int64_t)b * tiles + tile) * kSm;
   const bool fin = MERGED && d.defer_norm && d.t > 0;
   merge_partials_quad(sm, fin ? ws.fin + (((int64_t)b * d.T + d.t - 1) * tiles + tile) * 4 : nullptr, smf, smd);
-  TRACE(2, 3)
-  QTRACE(5)
 }
 
 template <bool MERGED>
 __global__ __launch_bounds__(4 * kTile) void tiled_prop_quad_kernel(const nfdpf_filter_desc d, TiledWs ws) {
-  quad_part<MERGED, false>(d, ws, nullptr);
+  quad_part<MERGED>(d, ws);
 }
-
-// ---- the fused step: front + nf_dyn inverse (fdyn_part), the row's x_dyn exchange
-// (row_sync), proposal + nf_dyn forward + cosine measurement (quad_part) -- one launch
-__global__ __launch_bounds__(4 * kTile) void tiled_step_fused_kernel(const nfdpf_filter_desc d, TiledWs ws) {
-  __shared__ FusedLds fx;
-  const uint32_t tag = (g_step_epoch << 16) + (uint32_t)d.t + 1u;
-  fdyn_part<true>(d, ws, &fx, tag);
-  TRACE(1, 0)
-  row_sync(d, ws, &fx, tag);
-  TRACE(1, 3)
-  quad_part<true, true>(d, ws, &fx);
-}
-__global__ void tiled_epoch_kernel() { g_step_epoch = g_step_epoch + 1u; }
 
 // ---- K3b (phase 2 of an EXTERNAL measurement): raw likelihood from lik_ext
 __global__ __launch_bounds__(kTile) void tiled_extlik_kernel(const nfdpf_filter_desc d, TiledWs ws) {
@@ -1893,7 +1548,6 @@ __global__ __launch_bounds__(kTile) void tiled_extlik_kernel(const nfdpf_filter_
 // last step -- the front kernel of the next step does it, see tiled_front_kernel)
 template <bool SHIFT>
 __global__ __launch_bounds__(kTile) void tiled_norm_kernel(const nfdpf_filter_desc d, TiledWs ws) {
-  TRACE(3, 0)
   __shared__ double shd[16];
   const int tiles = n_tiles(d.N);
   int b, tile;
@@ -1911,9 +1565,7 @@ __global__ __launch_bounds__(kTile) void tiled_norm_kernel(const nfdpf_filter_de
     sw = lw;
   }
   double *fin = ws.fin + (((int64_t)b * d.T + d.t) * tiles + tile) * 4;
-  TRACE(3, 2)
   store_sums4(fin, sp2, px, py, sw, shd);
-  TRACE(3, 3)
 }
 
 // per-row prediction / obs-likelihood sums of every step (after the last step)
@@ -2115,123 +1767,38 @@ static bool use_rows(const nfdpf_filter_desc &d) {
   return d.resampler == NFDPF_RESAMPLE_SOFT && !use_merged(d) && d.N > min_n;
 }
 
-// CRNVP weights staged in LDS per workgroup (tiled_prop_kernel<..., true>), opt-in with
-// NFDPF_CRNVP_STAGE=1 (read per call: tests compare both): 16-B aligned blobs and at most
-// kMaxFlows flows (<= 58 KB).  Measured SLOWER than the scalar-cache stream at C3 (48 vs 31 us
-// per launch, 1.11e9 vs 1.58e9; one ds_read_b128 per two v_pk_fma, 254 VGPRs leave the
-// compiler two or three reads in flight).
-static bool use_stage(const nfdpf_filter_desc &d) {
-  const char *e = getenv("NFDPF_CRNVP_STAGE");
-  if (!(e && e[0] == '1')) return false;
-  return d.n_flows >= 0 && d.n_flows <= kMaxFlows && ((uintptr_t)d.pe_params & 15) == 0 &&
-         ((uintptr_t)d.meas_params & 15) == 0;
+// One launch of `kern`.  With live timing requested (ev: the caller's event pair) the two events
+// ride in the launch's own dispatch (hipExtLaunchKernel: the kernel's begin / end timestamps),
+// not in separate event packets around it, so the measured time is the kernel's, as rocprof sees it.
+template <class... P, class... A>
+static void launch(void (*kern)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t st, hipEvent_t *ev,
+                   const A &...args) {
+  if (ev)
+    hipExtLaunchKernelGGL(kern, grid, block, (uint32_t)lds, st, ev[0], ev[1], 0, args...);
+  else
+    kern<<<grid, block, lds, st>>>(args...);
 }
 
-// The two-chain CRNVP proposal launch (tiled_prop_cm_kernel), opt-in with NFDPF_CM_TWO_CHAIN=1
-// (read per call: tests compare both).  Measured SLOWER than the one-chain tiled_prop_kernel at
-// C3 (33.7 vs 30.7 us per launch, 1.455e9 vs 1.566e9 particle-steps/s, one box, bit-identical).
-static bool use_cm(const nfdpf_filter_desc &d) {
-  const char *e = getenv("NFDPF_CM_TWO_CHAIN");
-  return e && e[0] == '1' && d.n_flows <= kMaxFlows;
-}
-
-// One launch per step (tiled_step_fused_kernel), opt-in with NFDPF_FUSED_STEP=1, when every
-// workgroup of the grid can be resident at once -- one 1024-thread workgroup per CU -- since a
-// row's four workgroups wait for each other inside it.  Measured SLOWER than the two launches
-// at C2 (1.483 vs 1.471 ms per pass, one box; profiles/r02_experiments.md): the granule
-// exchange itself costs ~0.8 us against the 1.65 us launch gap it removes, but the front half
-// runs 2.3 us longer inside the 16-wave workgroup than as its own 8-wave launch, and the
-// proposal half's prologue stays at 2 us.  Kept, bit-identical, for that record and as a base.
-static bool use_fused(const nfdpf_filter_desc &d) {
-  const char *e = getenv("NFDPF_FUSED_STEP");  // read per call: tests compare both paths
-  if (!(e && e[0] == '1') || !use_merged(d) || d.phase != 0 || n_tiles(d.N) > kFusedMaxTiles) return false;
-  // a sharded pass shares the device with the collectives' kernels on other streams, which can
-  // hold CUs while the row's workgroups spin on each other: never there
-  if (d.B_global != d.B) return false;
-  int dev = 0, cus = 0, occ = 0;
-  const size_t mlds = (size_t)(std::max(d.N, d.B_global) + 2 * d.N) * 4;
-  if (hipGetDevice(&dev) != hipSuccess ||
-      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-      hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, tiled_step_fused_kernel, 4 * kTile, mlds) != hipSuccess ||
-      occ < 1)
-    return false;
-  return (int64_t)n_tiles(d.N) * d.B <= (int64_t)cus * occ;
-}
-
-// The proposal launch.  With live timing requested (prof_events) the two events ride in the
-// launch's own dispatch (hipExtLaunchKernel: the kernel's begin / end timestamps), not in
-// separate event packets around it, so the measured time is the kernel's, as rocprof sees it.
+// The proposal launch.
 template <bool NFD, bool NFC, int MEAS>
 static void launch_prop(const nfdpf_filter_desc &d, TiledWs ws, dim3 g, hipStream_t st, hipEvent_t *ev) {
   // the two-role kernel needs a flow chain to overlap with the measurement
   // (a third role splitting the cosine encoder's output layer was measured slower: 16.7 vs
   // 11.4 us for the compute phase at C2 -- the extra waves duplicate the encoder's first layers)
   if constexpr (NFD && NFC && MEAS == NFDPF_MEAS_COS) {
-    if (use_merged(d)) {
-#ifndef NFDPF_PROP_SPLIT  // the quad launch (flow pair beside encoder pair); -DNFDPF_PROP_SPLIT: the pair launch
-      if (ev)
-        hipExtLaunchKernelGGL(tiled_prop_quad_kernel<true>, g, dim3(4 * kTile), 0, st, ev[0], ev[1], 0, d, ws);
-      else
-        tiled_prop_quad_kernel<true><<<g, 4 * kTile, 0, st>>>(d, ws);
-#else
-      if (ev)
-        hipExtLaunchKernelGGL(tiled_prop_split_kernel<true>, g, dim3(2 * kTile), 0, st, ev[0], ev[1], 0, d, ws);
-      else
-        tiled_prop_split_kernel<true><<<g, 2 * kTile, 0, st>>>(d, ws);
-#endif
-      return;
-    }
-    if (use_split(d)) {
-      if (ev)
-        hipExtLaunchKernelGGL(tiled_prop_split_kernel<false>, g, dim3(2 * kTile), 0, st, ev[0], ev[1], 0, d, ws);
-      else
-        tiled_prop_split_kernel<false><<<g, 2 * kTile, 0, st>>>(d, ws);
-      return;
-    }
-  }
-  if constexpr (!NFC && MEAS == NFDPF_MEAS_CRNVP) {
-    if (use_cm(d) && !d.meas_mfma) {
-      const size_t lds = cm_lds_bytes(d.n_flows);
-      // the fold buffer exceeds the default 64 KB at 3-4 flows
-      ensure_max_dynamic_lds((const void *)tiled_prop_cm_kernel<NFD>, (int)cm_lds_bytes(kMaxFlows));
-      if (ev)
-        hipExtLaunchKernelGGL(tiled_prop_cm_kernel<NFD>, g, dim3(2 * kTile), lds, st, ev[0], ev[1], 0, d, ws);
-      else
-        tiled_prop_cm_kernel<NFD><<<g, 2 * kTile, lds, st>>>(d, ws);
-      return;
-    }
+    // (merged: the quad launch, flow pair beside encoder pair)
+    if (use_merged(d)) return launch(tiled_prop_quad_kernel<true>, g, 4 * kTile, 0, st, ev, d, ws);
+    if (use_split(d)) return launch(tiled_prop_split_kernel, g, 2 * kTile, 0, st, ev, d, ws);
   }
   if constexpr (NFC && MEAS != NFDPF_MEAS_EXTERNAL) {
-    if (ev)
-      hipExtLaunchKernelGGL(tiled_prop2_kernel<NFD, NFC, MEAS, 2>, g, dim3(2 * kTile), 0, st, ev[0], ev[1], 0, d,
-                            ws);
-    else
-      tiled_prop2_kernel<NFD, NFC, MEAS, 2><<<g, 2 * kTile, 0, st>>>(d, ws);
+    launch(tiled_prop2_kernel<NFD, NFC, MEAS, 2>, g, 2 * kTile, 0, st, ev, d, ws);
   } else {
-    if constexpr (MEAS == NFDPF_MEAS_CRNVP) {
-      if (d.meas_mfma) {  // (NFC is false here: the tiled_prop2 branch above takes the conditional proposal)
-        const size_t lds = (size_t)crnvp_mfma_floats(d.n_flows) * sizeof(float);
-        if (ev)
-          hipExtLaunchKernelGGL(tiled_prop_kernel<NFD, NFC, MEAS, 2>, g, dim3(kTile), lds, st, ev[0], ev[1], 0, d,
-                                ws);
-        else
-          tiled_prop_kernel<NFD, NFC, MEAS, 2><<<g, kTile, lds, st>>>(d, ws);
-        return;
-      }
-      if (use_stage(d)) {
-        const size_t lds = (size_t)(kCrnvpPe + d.n_flows * kCrnvpFlow) * sizeof(float);
-        if (ev)
-          hipExtLaunchKernelGGL(tiled_prop_kernel<NFD, NFC, MEAS, 1>, g, dim3(kTile), lds, st, ev[0], ev[1], 0,
-                                d, ws);
-        else
-          tiled_prop_kernel<NFD, NFC, MEAS, 1><<<g, kTile, lds, st>>>(d, ws);
-        return;
-      }
+    if constexpr (MEAS == NFDPF_MEAS_CRNVP) {  // (NFC is false here: tiled_prop2 takes the conditional proposal)
+      if (d.meas_mfma)
+        return launch(tiled_prop_kernel<NFD, NFC, MEAS, true>, g, kTile,
+                      (size_t)crnvp_mfma_floats(d.n_flows) * sizeof(float), st, ev, d, ws);
     }
-    if (ev)
-      hipExtLaunchKernelGGL(tiled_prop_kernel<NFD, NFC, MEAS>, g, dim3(kTile), 0, st, ev[0], ev[1], 0, d, ws);
-    else
-      tiled_prop_kernel<NFD, NFC, MEAS><<<g, kTile, 0, st>>>(d, ws);
+    launch(tiled_prop_kernel<NFD, NFC, MEAS>, g, kTile, 0, st, ev, d, ws);
   }
 }
 
@@ -2328,8 +1895,6 @@ extern "C" int64_t nfdpf_filter_tiled_workspace_bytes(int B, int N, int T) {
 }
 
 extern "C" int nfdpf_filter_tiled_tiles(int N) { return N <= 0 ? 0 : n_tiles(N); }
-
-extern "C" int nfdpf_filter_tiled_fused(const nfdpf_filter_desc *d) { return d && use_fused(*d) ? 1 : 0; }
 
 extern "C" int nfdpf_ess_gate_tiled(const double *parts, int B, int N, int t, int force, int32_t *gate,
                                     void *stream) {
@@ -2437,22 +2002,6 @@ extern "C" int nfdpf_split_fault(int reset, void *stream) {
   return n;
 }
 
-#ifdef NFDPF_EXP_PTRACE
-extern "C" NFDPF_API int nfdpf_exp_ptrace_read(void *host) {
-  return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_ptrace), sizeof(g_ptrace)) == hipSuccess ? 0 : 1;
-}
-#endif
-#ifdef NFDPF_EXP_QTRACE
-extern "C" NFDPF_API int nfdpf_exp_qtrace_read(void *host) {
-  return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_qtrace), sizeof(g_qtrace)) == hipSuccess ? 0 : 1;
-}
-#endif
-#ifdef NFDPF_EXP_TRACE
-extern "C" NFDPF_API int nfdpf_exp_trace_read(void *host) {
-  return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_trace), sizeof(g_trace)) == hipSuccess ? 0 : 1;
-}
-#endif
-
 extern "C" int nfdpf_filter_step_tiled(const nfdpf_filter_desc *dp, void *workspace, void *stream) {
   NFDPF_REQUIRE(dp && workspace, "nfdpf_filter_step_tiled: null argument");
   const nfdpf_filter_desc &d = *dp;
@@ -2508,42 +2057,24 @@ extern "C" int nfdpf_filter_step_tiled(const nfdpf_filter_desc *dp, void *worksp
                                                          : (size_t)d.B_global * 4;
     // live timing of the front launch (the resampler's) in its own dispatch, as launch_prop
     hipEvent_t *fev = d.prof_events && d.prof_front ? (hipEvent_t *)d.prof_events + 2 : nullptr;
-    if (use_fused(d)) {  // the whole step in one launch (the live timing on it)
+    if (use_merged(d)) {
       const size_t mlds = (size_t)(std::max(d.N, d.B_global) + 2 * d.N) * 4;
-      if (d.t == 0) tiled_epoch_kernel<<<1, 1, 0, st>>>();  // new tags for this pass
-      hipEvent_t *ev = (hipEvent_t *)d.prof_events;
-      if (ev)
-        hipExtLaunchKernelGGL(tiled_step_fused_kernel, g, dim3(4 * kTile), mlds, st, ev[0], ev[1], 0, d, ws);
-      else
-        tiled_step_fused_kernel<<<g, 4 * kTile, mlds, st>>>(d, ws);
-    } else if (use_merged(d)) {
-      const size_t mlds = (size_t)(std::max(d.N, d.B_global) + 2 * d.N) * 4;
-      if (fev)
-        hipExtLaunchKernelGGL(tiled_fdyn_kernel, g, dim3(2 * kTile), mlds, st, fev[0], fev[1], 0, d, ws);
-      else
-        tiled_fdyn_kernel<<<g, 2 * kTile, mlds, st>>>(d, ws);
+      launch(tiled_fdyn_kernel, g, 2 * kTile, mlds, st, fev, d, ws);
     } else if (use_rows(d)) {
       // the gate / row normaliser / row resampling once per row, then the tiles without LDS
       tiled_rows_kernel<<<d.B, 1024, lds, st>>>(d, ws);
-      if (fev)
-        hipExtLaunchKernelGGL(tiled_front_kernel<true>, g, dim3(kTile), 0, st, fev[0], fev[1], 0, d, ws);
-      else
-        tiled_front_kernel<true><<<g, kTile, 0, st>>>(d, ws);
-    } else if (fev) {
-      hipExtLaunchKernelGGL(tiled_front_kernel<false>, g, dim3(kTile), lds, st, fev[0], fev[1], 0, d, ws);
+      launch(tiled_front_kernel<true>, g, kTile, 0, st, fev, d, ws);
     } else {
-      tiled_front_kernel<false><<<g, kTile, lds, st>>>(d, ws);
+      launch(tiled_front_kernel<false>, g, kTile, lds, st, fev, d, ws);
     }
-    if (use_fused(d))
-      ;  // the whole step ran in tiled_step_fused_kernel
-    else if (use_merged(d))
+    if (use_merged(d))
       ;  // nf_dyn ran in tiled_fdyn_kernel
     else if (use_split(d))
       tiled_dyn_kernel<true><<<g, 2 * kTile, 0, st>>>(d, ws);
     else if (d.nf_dyn)
       tiled_dyn_kernel<false><<<g, kTile, 0, st>>>(d, ws);
     hipEvent_t *ev = (hipEvent_t *)d.prof_events;
-    if (!use_fused(d)) switch (d.measurement) {
+    switch (d.measurement) {
       case NFDPF_MEAS_COS: dispatch_prop<NFDPF_MEAS_COS>(d, ws, g, st, ev); break;
       case NFDPF_MEAS_CRNVP: dispatch_prop<NFDPF_MEAS_CRNVP>(d, ws, g, st, ev); break;
       case NFDPF_MEAS_NN: dispatch_prop<NFDPF_MEAS_NN>(d, ws, g, st, ev); break;

@@ -49,14 +49,11 @@
 namespace nfdpf {
 
 // i (or j) per workgroup = the table slice length: 256, each lane carrying kR = 4 of the
-// workgroup's i.  -DNFDPF_OT_SL=128 builds a layout with twice the waves per launch (kR = 2,
-// the 4 waves split the slices four ways; 4 waves per SIMD at C4 instead of 2): measured
-// slower on one box (C4 90.4 vs 83.1 ms per pass, C3 forced 27.1 vs 25.5) -- the per-workgroup
-// prologue / epilogue doubles with the workgroup count.
-#ifndef NFDPF_OT_SL
-#define NFDPF_OT_SL 256
-#endif
-constexpr int kOtThreads = NFDPF_OT_SL;
+// workgroup's i.  128 gives a layout with twice the waves per launch (kR = 2, the 4 waves split
+// the slices four ways; 4 waves per SIMD at C4 instead of 2): measured slower on one box (C4
+// 90.4 vs 83.1 ms per pass, C3 forced 27.1 vs 25.5) -- the per-workgroup prologue / epilogue
+// doubles with the workgroup count.
+constexpr int kOtThreads = 256;
 constexpr int kOtBlock = 256;  // threads per workgroup; threads >= kOtThreads own no i
 static_assert(kOtThreads == 128 || kOtThreads == 256, "slice length");
 constexpr double kLog2ed = 1.4426950408889634;
@@ -66,38 +63,18 @@ constexpr float kLo = 0x1.0p-60f, kHi = 0x1.0p60f;  // outside: the lane recompu
 // lane's sum is ~1), i.e. c_ij <= 24 + (M_s - m_i): up to 96 every such K_ij = 2^-c_ij and
 // alpha_j K_ij stay >= 2^-120, normal fp32 (2^-126); only terms below 2^-24 of the sum can
 // underflow.  (60 in r01: late, small-epsilon iterations took the two-exp form on most slices.)
-#ifndef NFDPF_OT_RISKY
-#define NFDPF_OT_RISKY 96.f
-#endif
-constexpr float kRisky = NFDPF_OT_RISKY;
-// Prescaled coordinates (-DNFDPF_OT_PRESCALE): the iteration / final tables' X, Y planes and the
-// lanes' own points are multiplied by s = sqrt(sc) (sc = the base-2 cost scale of the table's
-// epsilon), so the pair exponent is -(dx'^2 + dy'^2) with no per-pair scaling multiply.
-// Measured (round 2d, one box): C4 +3 %, C3 forced +1 %, but the full-size C3 teacher-forced
-// likelihood error grows to 0.14 against the reference's own fp32 error of 0.0098 (the
-// difference of two prescaled coordinates rounds ~5x coarser on close pairs): not shipped.
-#ifdef NFDPF_OT_PRESCALE
-constexpr bool kPrescale = true;
-#else
-constexpr bool kPrescale = false;
-#endif
+constexpr float kRisky = 96.f;
+// (Prescaled coordinates -- the tables' X, Y planes and the lanes' own points multiplied by
+// sqrt(sc), so the pair exponent needs no per-pair scaling multiply -- measured C4 +3 %, C3
+// forced +1 % in round 2d on one box, but the full-size C3 teacher-forced likelihood error grew
+// to 0.14 against the reference's own fp32 error of 0.0098: the difference of two prescaled
+// coordinates rounds ~5x coarser on close pairs.  Never shipped; retired, f81620f is the last
+// commit that holds the code.)
 
 typedef float f2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ f2 sp2(float v) { return f2{v, v}; }
 __device__ __forceinline__ f2 pfma2(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }
 
-#ifdef NFDPF_OT_RISKSTAT  // experiment builds: share of wave-slices on the two-exp path, per call
-__device__ unsigned int g_ot_risky, g_ot_wslices;
-#endif
-#ifdef NFDPF_EXP_OTTRACE  // experiment builds: per-phase timestamps of every iteration launch, lane 0 of wave 0
-__device__ uint64_t g_ot_tr[1024][64][8], g_ot_loopend[1024];
-#define OTT_WG (blockIdx.y * gridDim.x + blockIdx.x)
-#define OTTRACE(k, slot)                                         \
-  if (threadIdx.x == 0 && OTT_WG < 1024)                         \
-    g_ot_tr[OTT_WG][(k) & 63][slot] = __builtin_amdgcn_s_memrealtime();
-#else
-#define OTTRACE(k, slot)
-#endif
 struct OtState {
   int32_t stopped;    // set by the iteration that observes a converged row
   int32_t K;          // total_iter of the reference
@@ -241,68 +218,19 @@ struct TBlock {  // 8 consecutive j of NP planes
   float4 v[NP][2];
 };
 
-// load block j of the planes pl[0..NP) of a row table
-// The words are wave-uniform.  -DNFDPF_OT_SLOAD reads them through the constant address space
-// (scalar loads into SGPRs, one block at a time) instead of the pipelined vector loads that
-// return the same 16 B to all 64 lanes: measured SLOWER (C4 iteration 124 vs 118 us, C3 22 vs
-// 17 us; the compiler keeps half of the words as vector loads and the scalar waits are not
-// overlapped -- profiles/r02_experiments.md).  So was one coalesced load per block handed out by
-// v_readlane as SGPR operands (C4 iteration 129-141 vs 117 us).
-typedef const float4 __attribute__((address_space(4))) cfloat4;
-template <int NP>
-__device__ __forceinline__ void tload(TBlock<NP> &B, const float *tab, int64_t Np, int j, const int (&pl)[NP]) {
-#pragma unroll
-  for (int p = 0; p < NP; ++p) {
-#if !defined(NFDPF_OT_SLOAD) || !defined(__HIP_DEVICE_COMPILE__)
-    const float4 *X = reinterpret_cast<const float4 *>(tab + pl[p] * Np + j);
-#else
-    cfloat4 *X = (cfloat4 *)(tab + pl[p] * Np + j);
-#endif
-    B.v[p][0] = X[0];
-    B.v[p][1] = X[1];
-  }
-}
-
+// (The table words are wave-uniform.  Reading them straight from global memory -- pipelined
+// 16-B vector loads that return the same words to all 64 lanes, or scalar loads through the
+// constant address space -- measured slower than the LDS-staged slices below: scalar C4
+// iteration 124 vs 118 us, C3 22 vs 17 us, profiles/r02_experiments.md; one coalesced load per
+// block handed out by v_readlane 129-141 vs 117 us.  Retired; f81620f is the last commit that
+// holds those loaders.)
 template <int NP>
 __device__ __forceinline__ f2 tpair(const TBlock<NP> &B, int p, int q) {
   const float4 &c = B.v[p][q >> 1];
   return (q & 1) ? f2{c.z, c.w} : f2{c.x, c.y};
 }
 
-// Software pipeline over blocks of 8 j in [j0, j1) (a multiple of 16) with vector loads of the
-// wave-uniform table words (vmcnt is in order, so a wait covers exactly the block about to be
-// used -- scalar loads return out of order and every wait on them is lgkmcnt(0)).  Two named
-// buffers; the scheduling barriers keep each block's loads one compute block ahead of their
-// use.  Past the end a prefetch reads the next plane / the allocation's padding block and is
-// discarded.
-template <int NP, class Body>
-__device__ __forceinline__ void pipelined(const float *tab, int64_t Np, int j0, int j1, const int (&pl)[NP],
-                                          const Body &body) {
-#ifdef NFDPF_OT_SLOAD
-  // scalar loads: one block at a time (a scalar wait is lgkmcnt(0), so a prefetched block would
-  // be waited for with the current one); the other waves of the SIMD cover the latency
-  for (int j = j0; j < j1; j += 8) {
-    TBlock<NP> A;
-    tload(A, tab, Np, j, pl);
-    body(A);
-  }
-  return;
-#endif
-  TBlock<NP> A, Bk;
-  tload(A, tab, Np, j0, pl);
-  for (int j = j0; j < j1; j += 16) {
-    tload(Bk, tab, Np, j + 8, pl);
-    __builtin_amdgcn_sched_barrier(0);
-    body(A);
-    __builtin_amdgcn_sched_barrier(0);
-    tload(A, tab, Np, j + 16, pl);
-    __builtin_amdgcn_sched_barrier(0);
-    body(Bk);
-    __builtin_amdgcn_sched_barrier(0);
-  }
-}
-
-// LDS-staged slices (default; -DNFDPF_OT_L1 keeps the wave-uniform vector loads above).  A
+// LDS-staged slices.  A
 // wave copies a whole slice (256 j of up to kSlicePl planes) with coalesced loads -- lane l
 // holds j0 + 4l .. j0 + 4l + 3 of every plane, 1 KB per plane and load instruction, all of it
 // used -- into its own LDS region, and the pair loop reads the wave-uniform words from there
@@ -346,12 +274,7 @@ __device__ __forceinline__ void lds_tblock(TBlock<NP> &B, const float *sl, int j
   }
 }
 // the 32 blocks of 8 j of a staged slice, one block read ahead
-#ifdef NFDPF_OT_LDS1
-constexpr bool kLds1 = true;
-#else
-constexpr bool kLds1 = false;
-#endif
-template <int NP, bool ONE = kLds1, class Body>
+template <int NP, bool ONE = false, class Body>
 __device__ __forceinline__ void slice_blocks(const float *sl, const int (&pl)[NP], const Body &body) {
   if constexpr (ONE) {  // one block at a time (32 fewer VGPRs; the SIMD's other waves cover the LDS latency)
     for (int j = 0; j < kOtThreads; j += 8) {
@@ -383,9 +306,7 @@ using LaneI = LaneIK<kR>;
 
 // Shifted-exponent block (planes X, Y, E_0..E_{NH-1}, V_0..V_{NV-1}; E = h - M_s):
 //   acc[r][w] += 2^(E_w[j] + o[r][w] - sc |p_i - p_j|^2),  accv[r][v] += (w = 0 term) V_v[j]
-// PS: prescaled points (the lane's and the table's X, Y times sqrt(sc)): the exponent is
-// E + o - (dx^2 + dy^2), nsc2 unused.
-template <int NH, int NV, int NP, bool PS = false, int KR>
+template <int NH, int NV, int NP, int KR>
 __device__ __forceinline__ void hblock(const TBlock<NP> &B, const LaneIK<KR> &L, f2 nsc2, const f2 (&o)[KR][NH],
                                        f2 (&acc)[KR][NH], f2 (&accv)[KR][NV > 0 ? NV : 1]) {
 #pragma unroll
@@ -394,11 +315,11 @@ __device__ __forceinline__ void hblock(const TBlock<NP> &B, const LaneIK<KR> &L,
     for (int r = 0; r < KR; ++r) {
       const f2 dx = L.x[r] - tpair(B, 0, q);
       const f2 dy = L.y[r] - tpair(B, 1, q);
-      const f2 d2 = (PS && NH == 1) ? f2{} : pfma2(dy, dy, dx * dx);
+      const f2 d2 = pfma2(dy, dy, dx * dx);
 #pragma unroll
       for (int w = 0; w < NH; ++w) {
         const f2 eo = tpair(B, 2 + w, q) + o[r][w];
-        const f2 a = !PS ? pfma2(nsc2, d2, eo) : NH == 1 ? pfma2(-dy, dy, pfma2(-dx, dx, eo)) : eo - d2;
+        const f2 a = pfma2(nsc2, d2, eo);
         const f2 t = f2{__builtin_amdgcn_exp2f(a.x), __builtin_amdgcn_exp2f(a.y)};
         acc[r][w] += t;
         if (w == 0)
@@ -419,7 +340,7 @@ __device__ __forceinline__ void kblock(const TBlock<4> &B, const LaneIK<KR> &L, 
     for (int r = 0; r < KR; ++r) {
       const f2 dx = L.x[r] - tpair(B, 0, q);
       const f2 dy = L.y[r] - tpair(B, 1, q);
-      const f2 a = kPrescale ? -pfma2(dy, dy, dx * dx) : pfma2(dy, dy, dx * dx) * nsc2;
+      const f2 a = pfma2(dy, dy, dx * dx) * nsc2;
       const f2 k = f2{__builtin_amdgcn_exp2f(a.x), __builtin_amdgcn_exp2f(a.y)};
       acc[r][0] = pfma2(tpair(B, 2, q), k, acc[r][0]);
       acc[r][1] = pfma2(tpair(B, 3, q), k, acc[r][1]);
@@ -428,7 +349,6 @@ __device__ __forceinline__ void kblock(const TBlock<4> &B, const LaneIK<KR> &L, 
 }
 
 __device__ __forceinline__ float hsum2(f2 a) { return a.x + a.y; }
-__device__ __forceinline__ bool risky_any(bool r) { return __builtin_amdgcn_ballot_w64(r) != 0; }
 
 // slice offset M_s - m_i in fp32 (-inf: the slice carries no weight)
 __device__ __forceinline__ float slice_off(double Ms, double m) {
@@ -474,22 +394,10 @@ __device__ __forceinline__ void combine(float *lds, const float (&mine)[KR][NK],
   }
 }
 
-// the scale of prescaled points (kPrescale): identical in the table writers and the pair loops
-__device__ __forceinline__ float pscale(float sc) { return sqrtf(sc); }
-template <int KR>
-__device__ __forceinline__ void prescale(LaneIK<KR> &L, float sc) {
-  const f2 s = sp2(pscale(sc));
-#pragma unroll
-  for (int r = 0; r < KR; ++r) {
-    L.x[r] *= s;
-    L.y[r] *= s;
-  }
-}
-
 // Workgroup sums over the whole row with the shifted-exponent block (table planes 0, 1,
 // 2 .. 2+NH+NV, slice maxima msh[s * MS + w]): thread t gets, for i = 256 s0 + t,
 //   S[w] = sum_j 2^(h_w[j] - sc |p_i - p_j|^2 - m_i[w]),  SV[v] = sum_j (w = 0 term) V_v[j].
-template <int NH, int NV, int MS, bool PS = false, class Pt>
+template <int NH, int NV, int MS, class Pt>
 __device__ __forceinline__ void wg_table_sums(const float *tab, const double *msh, int splits, int64_t Np, int N,
                                               float sc, const Pt &pt, float *lds, float (&S)[NH], float *SV) {
   constexpr int NP = 2 + NH + NV;
@@ -499,7 +407,6 @@ __device__ __forceinline__ void wg_table_sums(const float *tab, const double *ms
   LaneI L;
   double m[kR][NH];
   lane_points<NH>(N, pt, L, m);
-  if (PS) prescale(L, sc);
   const f2 nsc2 = sp2(-sc);
   f2 acc[kR][NH], accv[kR][NV > 0 ? NV : 1];
 #pragma unroll
@@ -510,22 +417,15 @@ __device__ __forceinline__ void wg_table_sums(const float *tab, const double *ms
     for (int v = 0; v < NV; ++v) accv[r][v] = sp2(0.f);
   }
   const int w0 = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-#ifndef NFDPF_OT_L1
   float *sl = lds + kLdsPart + w0 * kSliceFloats;
-#endif
   for (int s = w0; s < splits; s += kWaves) {
     f2 o[kR][NH];
 #pragma unroll
     for (int r = 0; r < kR; ++r)
 #pragma unroll
       for (int w = 0; w < NH; ++w) o[r][w] = sp2(slice_off(msh[s * MS + w], m[r][w]));
-#ifndef NFDPF_OT_L1
     slice_copy<NP>(tab, Np, s * kOtThreads, sl);
-    slice_blocks<NP>(sl, pl, [&](const TBlock<NP> &B) { hblock<NH, NV, NP, PS>(B, L, nsc2, o, acc, accv); });
-#else
-    pipelined<NP>(tab, Np, s * kOtThreads, (s + 1) * kOtThreads, pl,
-                  [&](const TBlock<NP> &B) { hblock<NH, NV, NP, PS>(B, L, nsc2, o, acc, accv); });
-#endif
+    slice_blocks<NP>(sl, pl, [&](const TBlock<NP> &B) { hblock<NH, NV, NP>(B, L, nsc2, o, acc, accv); });
   }
   float mine[kR][NH + NV], out[NH + NV];
 #pragma unroll
@@ -567,7 +467,6 @@ __device__ __forceinline__ void wg_iter_sums(const float *tab, const double *msh
     L.x[r] = rbase ? La.x[(kR - KR + r) % kR] : La.x[r];
     L.y[r] = rbase ? La.y[(kR - KR + r) % kR] : La.y[r];
   }
-  if (kPrescale) prescale(L, sc);
   const f2 nsc2 = sp2(-sc);
   float Sk[KR][2];
   f2 hacc[KR][2];
@@ -578,9 +477,7 @@ __device__ __forceinline__ void wg_iter_sums(const float *tab, const double *msh
     hacc[r][0] = hacc[r][1] = sp2(0.f);
   }
   const int w0 = wv % kWaves;  // the wave's slice set
-#ifndef NFDPF_OT_L1
   float *sl = lds + kLdsPart + wv * kSliceFloats;
-#endif
   for (int s = w0; s < splits; s += kWaves) {
     const double Ma = msh[2 * s], Mb = msh[2 * s + 1];
     float oa4[kR], ob4[kR], oa[KR], ob[KR];
@@ -597,19 +494,9 @@ __device__ __forceinline__ void wg_iter_sums(const float *tab, const double *msh
       ob[r] = rbase ? ob4[(kR - KR + r) % kR] : ob4[r];
     }
     const int j0 = s * kOtThreads, j1 = j0 + kOtThreads;
-#ifndef NFDPF_OT_L1
     slice_copy<6>(tab, Np, s * kOtThreads, sl);
     (void)j1;
-#define OT_SLICE_LOOP(PL, ...) slice_blocks<4, kLds1 || W != kWaves>(sl, PL, __VA_ARGS__)
-#else
-#define OT_SLICE_LOOP(PL, ...) pipelined<4>(tab, Np, j0, j1, PL, __VA_ARGS__)
-#endif
-#ifdef NFDPF_OT_RISKSTAT
-    if ((threadIdx.x & 63) == 0) {
-      atomicAdd(&g_ot_wslices, 1u);
-      if (risky_any(risky)) atomicAdd(&g_ot_risky, 1u);
-    }
-#endif
+#define OT_SLICE_LOOP(PL, ...) slice_blocks<4, W != kWaves>(sl, PL, __VA_ARGS__)
     if (__builtin_amdgcn_ballot_w64(risky) == 0) {
       f2 acc[KR][2];
 #pragma unroll
@@ -627,13 +514,10 @@ __device__ __forceinline__ void wg_iter_sums(const float *tab, const double *msh
         o[r][0] = sp2(oa[r]);
         o[r][1] = sp2(ob[r]);
       }
-      OT_SLICE_LOOP(plh, [&](const TBlock<4> &B) { hblock<2, 0, 4, kPrescale>(B, L, nsc2, o, hacc, none); });
+      OT_SLICE_LOOP(plh, [&](const TBlock<4> &B) { hblock<2, 0, 4>(B, L, nsc2, o, hacc, none); });
     }
 #undef OT_SLICE_LOOP
   }
-#ifdef NFDPF_EXP_OTTRACE
-  if (threadIdx.x == 0 && OTT_WG < 1024) g_ot_loopend[OTT_WG] = __builtin_amdgcn_s_memrealtime();
-#endif
   float mine[KR][2], out[2];
 #pragma unroll
   for (int r = 0; r < KR; ++r) {
@@ -784,10 +668,6 @@ __global__ __launch_bounds__(kOtBlock) void ot_setup_kernel(const float *__restr
       e = fmax(e * P.sf, P.eps);
     }
     if (b == 0) {
-#ifdef NFDPF_OT_RISKSTAT
-      g_ot_risky = 0;
-      g_ot_wslices = 0;
-#endif
       ws.st->stopped = 0;
       ws.st->K = 0;
       ws.st->fallbacks = 0;
@@ -797,9 +677,8 @@ __global__ __launch_bounds__(kOtBlock) void ot_setup_kernel(const float *__restr
   const int i = s0i + threadIdx.x;
   const bool v = i < N && threadIdx.x < kOtThreads;
   const double h[2] = {v ? (double)lwf(i) * kLog2ed : 0.0, logu * kLog2ed};
-  const float sc = kPrescale ? pscale(cost_scale(1.0 / eps0)) : 1.f;  // ot_init's epsilon
-  write_col<2, 0, true>(tabI_row(ws, P, 1, b), mI_row(ws, P, 1, b), np_of(P), v, v ? sx(i) * sc : 0.f,
-                        v ? sy(i) * sc : 0.f, h, nullptr, shd);
+  write_col<2, 0, true>(tabI_row(ws, P, 1, b), mI_row(ws, P, 1, b), np_of(P), v, v ? sx(i) : 0.f, v ? sy(i) : 0.f, h,
+                        nullptr, shd);
 }
 
 // Table columns of state `ks` (the potentials a_y, b_x of thread i just produced): for the
@@ -823,16 +702,10 @@ __device__ __forceinline__ void emit_state_tables(const OtParams &P, const OtWs 
   M[4] = dmax ? *dmax : 0.0;
   block_max_n<5>(M, shd);
   if (dmax) *dmax = M[4];
-  {
-    const float s = kPrescale ? pscale(cost_scale(inv)) : 1.f;
-    write_col_m<2, 0, true>(tabI_row(ws, P, ks & 1, b), mI_row(ws, P, ks & 1, b), Np, v, xi * s, yi * s, hI, M,
-                            nullptr);
-  }
-  if (fin) {
-    const float s = kPrescale ? pscale(cost_scale(invF)) : 1.f;
-    write_col_m<2, 0, false>(ws.tabF + (int64_t)b * 4 * Np, ws.mF + (int64_t)b * P.splits * 2, Np, v, xi * s,
-                             yi * s, hF, M + 2, nullptr);
-  }
+  write_col_m<2, 0, true>(tabI_row(ws, P, ks & 1, b), mI_row(ws, P, ks & 1, b), Np, v, xi, yi, hI, M, nullptr);
+  if (fin)
+    write_col_m<2, 0, false>(ws.tabF + (int64_t)b * 4 * Np, ws.mF + (int64_t)b * P.splits * 2, Np, v, xi, yi, hF,
+                             M + 2, nullptr);
 }
 
 // the two softmins of an iteration for thread t's i (shifts ma / mb, base 2), from the
@@ -903,14 +776,10 @@ __device__ __forceinline__ bool ot_stop_before(const OtParams &P, const OtWs &ws
 }
 
 // iteration k: state k (buffer k&1) -> state k+1 (buffer (k+1)&1)  (apply_one :131-153)
-#ifndef NFDPF_OT_ITER_WPS
-#define NFDPF_OT_ITER_WPS 1
-#endif
 template <int W>
-__global__ __launch_bounds__(64 * W, W == 2 * kWaves ? 4 : NFDPF_OT_ITER_WPS) void ot_iter_kernel(
+__global__ __launch_bounds__(64 * W, W == 2 * kWaves ? 4 : 1) void ot_iter_kernel(
     OtParams P, OtWs ws, int k) {
   const bool lead = blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0;
-  OTTRACE(k, 0)
   if (ot_off(P)) {
     if (lead && P.host) host_flag(P.host, 0, P.seq);  // nothing to iterate: stop enqueueing
     return;
@@ -935,7 +804,6 @@ __global__ __launch_bounds__(64 * W, W == 2 * kWaves ? 4 : NFDPF_OT_ITER_WPS) vo
   }
   __syncthreads();
   if (s_stop) return;
-  OTTRACE(k, 1)
   const int b = blockIdx.y, N = P.N;
   const int i = blockIdx.x * kOtThreads + threadIdx.x;
   const bool v = i < N && threadIdx.x < kOtThreads;
@@ -960,10 +828,6 @@ __global__ __launch_bounds__(64 * W, W == 2 * kWaves ? 4 : NFDPF_OT_ITER_WPS) vo
       },
       [&](int j) { return ((double)lw[j] + bx[j] * inv) * kLog2ed; },
       [&](int j) { return (logu + ay[j] * inv) * kLog2ed; }, lds, A, Bv, &ws.st->fallbacks);
-  OTTRACE(k, 3)
-#ifdef NFDPF_EXP_OTTRACE
-  if (threadIdx.x == 0 && OTT_WG < 1024) g_ot_tr[OTT_WG][k & 63][2] = g_ot_loopend[OTT_WG];
-#endif
   double na = 0.0, nb = 0.0, dmax = 0.0;
   if (v) {
     na = 0.5 * (oa + A);
@@ -972,15 +836,7 @@ __global__ __launch_bounds__(64 * W, W == 2 * kWaves ? 4 : NFDPF_OT_ITER_WPS) vo
     pot_ptr(ws, P, k + 1, 1, b)[i] = nb;
     dmax = fmax(fabs(na - oa), fabs(nb - ob));
   }
-  OTTRACE(k, 4)
   emit_state_tables(P, ws, b, k + 1, v, xi, yi, v ? lw[i] : 0.f, logu, na, nb, shd, &dmax);
-  OTTRACE(k, 5)
-#ifdef NFDPF_EXP_OTTRACE
-  if (threadIdx.x == 0 && OTT_WG < 1024) {
-    g_ot_tr[OTT_WG][k & 63][6] = __builtin_amdgcn_s_getreg(4 | (31 << 11));   // HW_ID (CU, SIMD, SE)
-    g_ot_tr[OTT_WG][k & 63][7] = __builtin_amdgcn_s_getreg(20 | (31 << 11));  // XCC_ID
-  }
-#endif
   if (threadIdx.x == 0) ws.res[((int64_t)(k & 1) * P.B + b) * P.splits + blockIdx.x] = dmax;
 }
 
@@ -1032,7 +888,7 @@ __global__ __launch_bounds__(kOtBlock) void ot_final_kernel(OtParams P, OtWs ws)
   const float xi = v ? xs[2 * i] : 0.f, yi = v ? xs[2 * i + 1] : 0.f;
   const double sh = -inv * kLog2ed;  // f is the softmin that a_y converged to
   float S[1];
-  wg_table_sums<1, 0, 2, kPrescale>(tab, msh, P.splits, Np, N, sc,
+  wg_table_sums<1, 0, 2>(tab, msh, P.splits, Np, N, sc,
                          [&](int ii, float &x, float &y, double (&m)[1]) {
                            x = xs[2 * ii];
                            y = xs[2 * ii + 1];
@@ -1266,12 +1122,6 @@ static int ot_iter_waves(int /*wgs*/) {
   return (e && atoi(e) == 2 * kWaves) ? 2 * kWaves : kWaves;
 }
 
-#ifdef NFDPF_EXP_OTTRACE
-extern "C" __attribute__((visibility("default"))) int nfdpf_exp_ottrace(uint64_t *host) {
-  return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_ot_tr), sizeof(g_ot_tr)) == hipSuccess ? 0 : -1;
-}
-#endif
-
 extern "C" int64_t nfdpf_ot_workspace_bytes(int B, int N) {
   return (B <= 0 || N <= 0) ? 256 : ws_bytes(B, N);
 }
@@ -1283,13 +1133,6 @@ extern "C" int nfdpf_ot_stats(const void *workspace, int32_t *host_out) {
     return launch_status("nfdpf_ot_stats");
   host_out[0] = st.stopped ? st.K + 2 : -1;
   host_out[1] = st.fallbacks;
-#ifdef NFDPF_OT_RISKSTAT  // per-mille of wave-slices on the two-exp path instead
-  unsigned int rk = 0, ns = 0;
-  if (hipMemcpyFromSymbol(&rk, HIP_SYMBOL(g_ot_risky), sizeof(rk)) != hipSuccess ||
-      hipMemcpyFromSymbol(&ns, HIP_SYMBOL(g_ot_wslices), sizeof(ns)) != hipSuccess)
-    return launch_status("nfdpf_ot_stats");
-  host_out[1] = ns ? (int32_t)((1000ull * rk) / ns) : -1;
-#endif
   return NFDPF_OK;
 }
 

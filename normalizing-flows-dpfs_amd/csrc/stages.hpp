@@ -269,10 +269,8 @@ __device__ __forceinline__ float stage_propose_inverse(const nfdpf_filter_desc &
   const int nsC = net_size<1, kH>(oC);
   float lo[1] = {in.xd0}, up[1] = {in.xd1};
   float ld = 0.f;
-#ifndef NFDPF_EXP_NOCOND
   for (int f = d.n_flows - 1; f >= 0; --f)
     ld += coupling_inverse<1, kH>(wptr2(d.cond_params) + f * 2 * nsC, oC, lo, up, cb_cond + f * 2 * kH);
-#endif
   q0x = lo[0];
   q1x = up[0];
   return -ld;
@@ -293,7 +291,6 @@ __device__ __forceinline__ void stage_prior(const nfdpf_filter_desc &d, const Ro
     if (NFD) {
       float lo[1] = {q0x}, up[1] = {q1x};
       float ld2 = 0.f;
-#ifndef NFDPF_EXP_NODYNF
       if (d.nf_dyn == NFDPF_DYN_MAF) {
         // NormalizingFlowModel.forward over MAF flows (nf/models.py:13-21)
         float v[2] = {lo[0], up[0]};
@@ -305,7 +302,6 @@ __device__ __forceinline__ void stage_prior(const nfdpf_filter_desc &d, const Ro
           ld2 += coupling_forward<1, kH>(wptr2(d.dyn_params) + f * 2 * kNsDyn, kOctxDyn, lo, up,
                                          cb_dyn + f * 2 * kH);
       }
-#endif
       prior = density(lo[0] - r0, up[0] - r1, K, two_var) - (-ld2);
     } else {
       prior = density(q0x - r0, q1x - r1, K, two_var);
@@ -325,9 +321,6 @@ __device__ __forceinline__ void stage_prior(const nfdpf_filter_desc &d, const Ro
 template <int MEAS>
 __device__ __forceinline__ float stage_measure(const nfdpf_filter_desc &d, const StepShared &L, float q0x,
                                                float q1x) {
-#ifdef NFDPF_EXP_NOMEAS
-  return q0x * 1e-3f;
-#endif
   if (MEAS != NFDPF_MEAS_EXTERNAL)
     return measure<MEAS>(MeasArgs{d.pe_params, d.meas_params, d.n_flows, d.meas_prior_std}, L, q0x, q1x);
   return 0.f;

@@ -135,7 +135,6 @@ SIGNATURES = {
     "nfdpf_filter_step": (c_int, [POINTER(FilterDesc), c_void_p]),
     "nfdpf_filter_tiled_workspace_bytes": (c_int64, [c_int, c_int, c_int]),
     "nfdpf_filter_tiled_tiles": (c_int, [c_int]),
-    "nfdpf_filter_tiled_fused": (c_int, [POINTER(FilterDesc)]),
     "nfdpf_filter_desc_size": (c_int64, []),
     "nfdpf_filter_tiled_init": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "nfdpf_host_mapped_alloc": (c_int, [c_int64, c_void_p, c_void_p]),

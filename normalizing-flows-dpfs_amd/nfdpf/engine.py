@@ -660,7 +660,7 @@ class FilterEngine:
         fired = [] if host_mode else None
         self.last_ot_calls = 0
         ot_its = []  # the device-gated Sinkhorn calls' iteration counts (0: the gate was off)
-        self.last_fused = False  # the step ran as one launch (tiled_step_fused_kernel), set at t = 0
+        self.last_fused = False  # always: the one-launch step is retired (bench.py still reads this)
         keep = []  # host uploads must outlive their kernels
         # per-step pointers precomputed as integers: the loop below is the launch path of every
         # time step, so it stays free of tensor slicing and per-call lookups
@@ -818,8 +818,6 @@ class FilterEngine:
                     d.ot_x = xo.data_ptr()  # (read by the step only where the gate fired)
                 else:
                     d.ot_x = xin.data_ptr()  # not read: the motion stage keeps the previous particles
-            if t == 0 and tiled and not external:
-                self.last_fused = bool(L.lib().nfdpf_filter_tiled_fused(d_ref))
             d.prof_events = None
             d.prof_front = 0
             ev = None
@@ -829,12 +827,12 @@ class FilterEngine:
             every = c.kernel == "tiled" and not external
             if self.step_events is not None and (every or t == T // 2):
                 from .prof import EventPair
-                ev = EventPair(4 if every and not self.last_fused else 2)
+                ev = EventPair(4 if every else 2)
                 self.step_events.append(ev)
                 if not external:
                     d.prof_events = ev.ptr  # around the step's dominant launch, inside the library
-                    # and, tiled, around its front (resampling) launch -- none in the fused step
-                    d.prof_front = int(every and not self.last_fused)
+                    # and, tiled, around its front (resampling) launch
+                    d.prof_front = int(every)
             if external:
                 d.phase = 1
                 step()
@@ -862,11 +860,8 @@ class FilterEngine:
         # a wave-pair hand-off that timed out leaves stale data (csrc/split.hpp): fail loudly
         # (a stream-ordered read and a sync: deferred to finish_pending when the caller asked
         # for a pass free of host syncs)
-        # (the split nets, and the CRNVP launch's cond -> flow hand-off without --NF-cond)
-        # (the opt-in two-chain CRNVP launch hands off between its waves too; the default
-        # one-chain launch does not, and then no check -- a host sync -- is paid)
-        handoffs = d.split_nets or (d.measurement == L.MEAS["CRNVP"] and not d.nf_cond
-                                    and os.environ.get("NFDPF_CM_TWO_CHAIN", "0") == "1")
+        # (only the split nets hand off between waves: elsewhere no check -- a host sync -- is paid)
+        handoffs = d.split_nets
         capturing = torch.cuda.is_current_stream_capturing()
         check_split = tiled and handoffs and not capturing
         if record:  # the exact run's gates: the plan of the next passes
