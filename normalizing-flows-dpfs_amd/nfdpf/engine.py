@@ -21,11 +21,10 @@ Batch sharding (world size > 1, rows [rank B, (rank + 1) B) per rank):
 from __future__ import annotations
 
 import ctypes
-import math
 import os
 import time
 from dataclasses import dataclass, field
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -140,6 +139,28 @@ class FilterResult:
     def as_tuple(self):
         return (self.particles, self.probs, self.noise, self.lik, self.init_logw, self.index, self.jac,
                 self.prior, self.obs_likelihood)
+
+
+class Verify(NamedTuple):  # a one-shard pass's verification on the device (the pass's epilogue, or ops.pass_verify)
+    flags_dev: Optional[torch.Tensor]  # {fired, faults, done} int32 in device memory; None: mapped from host memory
+    obs: torch.Tensor                  # the obs-likelihood it reduced (valid whether or not a gate fired)
+    flags_host: object                 # ... the flags' host mapping (ops.HostMapped), else None
+    lease: object                      # ... and the lease of their slot when a captured graph holds it
+
+
+class Pending(NamedTuple):  # what run() leaves for finish_pending() (take_pending() hands it out; bench.py indexes it)
+    parts: Optional[torch.Tensor]   # [T, B, tiles, 4] fp64, step t's input softmax partials (None: decided pass)
+    tot: Optional[torch.Tensor]     # fp64 [T] log-weight sums per step; None: reduced on the device (verify.obs)
+    shard: "ShardInfo"
+    N: int
+    res: "FilterResult"             # its obs_likelihood is filled in by finish_pending
+    split_dev: object               # the device whose hand-off fault counter is still to be read, else None
+    verify: Optional[Verify]        # None: verified from ``parts`` (sharded: over the gathered rows)
+    was_pass: bool                  # ran as the one-launch pass (a fault turns it off; step launches raise)
+    decided: bool                   # the gates were decided inside the launch: only the fault flags are checked
+    plan: Optional[np.ndarray]      # the plan followed (np.int32 [T]), else None
+    gates: Optional[torch.Tensor]   # one shard's one-launch pass: its actual gates [T] int32 (a miss's new plan)
+    stage: list                     # stage_flags' pinned host copies: [flags], or sharded [gates + faults, tot]
 
 
 class FilterEngine:
@@ -876,8 +897,8 @@ class FilterEngine:
             check_split = False
             if pass_out is not None and (capturing or not finish):
                 res = FilterResult(hx, hp, hn, hl, logw0, hi, hj, hr, pass_out[2], pred, fired)
-                verify = [pass_out[1] if flags_host is None else None, pass_out[2], flags_host, flags_lease]
-                self._pending = (None, None, shard, N, res, None, verify, True, True)
+                verify = Verify(pass_out[1] if flags_host is None else None, pass_out[2], flags_host, flags_lease)
+                self._pending = Pending(None, None, shard, N, res, None, verify, True, True, None, None, [])
                 return res
             if not capturing:
                 if xg_pass:  # (the epilogue read and cleared this rank's fault counter)
@@ -920,14 +941,11 @@ class FilterEngine:
             res = FilterResult(hx, hp, hn, hl, logw0, hi, hj, hr, None, pred, fired)
             verify = None
             if verify_dev:
-                verify = [pass_out[1] if flags_host is None else None, pass_out[2], flags_host, flags_lease] \
-                    if pass_out is not None else list(ops.pass_verify(ess_hist[:T], lw_sum, N)[1:]) + [None, None]
+                verify = Verify(pass_out[1] if flags_host is None else None, pass_out[2], flags_host, flags_lease) \
+                    if pass_out is not None else Verify(*ops.pass_verify(ess_hist[:T], lw_sum, N)[1:], None, None)
                 check_split = False
-            # (+ the plan followed, and one shard's actual gates: a miss's new plan)
-            # (+ the plan followed, one shard's actual gates, and -- sharded -- the staged verification,
-            # stage_flags)
-            self._pending = (ess_hist[:T], tot, shard, N, res, dev if check_split else None, verify, use_pass, False,
-                             plan_arr, pass_out[0] if pass_out is not None else None, [])
+            self._pending = Pending(ess_hist[:T], tot, shard, N, res, dev if check_split else None, verify, use_pass,
+                                    False, plan_arr, pass_out[0] if pass_out is not None else None, [])
             if not finish:
                 return res  # the caller verifies (finish_pending, e.g. after each graph replay)
             ok = self.finish_pending()
@@ -990,29 +1008,25 @@ class FilterEngine:
         ``finish_pending(pending, synced=True)`` reads them with no stream operation -- so a
         later pass already queued keeps running (pipelined passes, bench.py).  Not while
         capturing a graph (the pinned allocation is not capturable): after the replay."""
-        verify = pending[6]
-        parts, tot, shard, N = pending[:4]
-        if verify is None and shard is not None and shard.world > 1 and len(pending) > 11:
+        verify, shard, stage = pending.verify, pending.shard, pending.stage
+        if verify is None and shard is not None and shard.world > 1:
             # sharded: the all-gather and the gates enqueued now, their small result copied to
             # pinned host memory behind them (every rank stages the same sequence of collectives)
-            dev_small, tot_all = FilterEngine._sharded_verify(parts, tot, shard, N)
+            dev_small, tot_all = FilterEngine._sharded_verify(pending.parts, pending.tot, shard, pending.N)
             host = torch.empty(dev_small.shape, dtype=dev_small.dtype, pin_memory=True)
             host.copy_(dev_small, non_blocking=True)
-            pending[11][:] = [host, tot_all]
-            return
-        if verify is None or verify[0] is None:  # (flags already mapped from host memory)
-            return
-        if verify[2] is None:
-            verify[2] = torch.empty(verify[0].shape, dtype=verify[0].dtype, pin_memory=True)
-        verify[2].copy_(verify[0], non_blocking=True)
+            stage[:] = [host, tot_all]
+        elif verify is not None and verify.flags_dev is not None:  # (else: flags already mapped from host memory)
+            if not stage:  # (the pinned buffer is kept across replays)
+                stage.append(torch.empty(verify.flags_dev.shape, dtype=verify.flags_dev.dtype, pin_memory=True))
+            stage[0].copy_(verify.flags_dev, non_blocking=True)
 
     @staticmethod
     def arm_flags(pending):
         """Before replaying a captured speculative pass whose flags are mapped from host memory:
         clear its completion word (the epilogue sets it, last, with a system-scope release)."""
-        verify = pending[6]
-        if verify is not None and verify[0] is None:
-            verify[2][2] = 0
+        if pending.verify is not None and pending.verify.flags_dev is None:
+            pending.verify.flags_host[2] = 0
 
     @staticmethod
     def wait_flags(pending, timeout_s: float = 60.0) -> bool:
@@ -1021,10 +1035,10 @@ class FilterEngine:
         Spins with a yield for the first millisecond, then sleeps 50 us between reads; every 10 ms
         it asks whether the current stream is idle -- an idle stream with the word still unset
         means the pass never ran (a launch or stream error): raised at once, not after the bound."""
-        verify = pending[6]
-        if verify is None or verify[0] is not None:
+        verify = pending.verify
+        if verify is None or verify.flags_dev is not None:
             return False
-        view = verify[2]
+        view = verify.flags_host
         t0 = time.perf_counter()
         last_q = t0
         while int(view[2]) == 0:
@@ -1056,11 +1070,21 @@ class FilterEngine:
         reduced (valid whether or not a gate fired); ``parts`` [T, B, tiles, 4] fp64, step t's
         input softmax partials; ``flags`` (gates fired, hand-off faults, written), host ints.
         The caller has synchronised the pass's stream."""
-        verify = pending[6]
-        if verify is None or not pending[7] or len(pending) < 11 or pending[10] is None:
+        verify = pending.verify
+        if verify is None or not pending.was_pass or pending.gates is None:
             raise L.NfdpfError("pending_pass_state: not the state of a one-shard speculative one-launch pass")
-        flags = verify[2][:3] if verify[0] is None else verify[0].tolist()[:3]
-        return dict(gates=pending[10], obs=verify[1], parts=pending[0], flags=tuple(int(v) for v in flags))
+        flags = verify.flags_host[:3] if verify.flags_dev is None else verify.flags_dev.tolist()[:3]
+        return dict(gates=pending.gates, obs=verify.obs, parts=pending.parts, flags=tuple(int(v) for v in flags))
+
+    def _faulted(self, faults, was_pass) -> bool:
+        """Hand-off faults: raised for the step launches; the one-launch pass is turned off (last_verify "fault")."""
+        if faults and not was_pass:
+            raise L.NfdpfError(f"nfdpf_filter_step_tiled: {faults} wave hand-off(s) timed out on the device "
+                               f"(outputs invalid)")
+        if faults:
+            self._pass_fault(faults, 4)
+            self.last_verify = "fault"
+        return bool(faults)
 
     def finish_pending(self, pending=None, synced: bool = False) -> bool:
         """Verify the speculative pass of the last ``run`` (or the given ``take_pending()``
@@ -1077,90 +1101,66 @@ class FilterEngine:
         copy has completed: they are read from pinned host memory with no stream operation, so a
         later pass already queued behind it keeps running (pipelined passes, bench.py)."""
         pend = pending if pending is not None else self._pending
-        parts, tot, shard, N, res, split_dev, verify, was_pass = pend[:8]
-        decided = len(pend) > 8 and pend[8]  # the gates were decided inside the launch
-        # a plan pass: the plan it followed, and one shard's actual gates (its epilogue's)
-        plan, gates_dev = (pend[9], pend[10]) if len(pend) > 10 else (None, None)
+        parts, tot, shard, verify, stage = pend.parts, pend.tot, pend.shard, pend.verify, pend.stage
         self.last_verify = "ok"
         if verify is not None:  # the device verification's flags: the one host synchronisation
-            if verify[0] is None:  # mapped from host memory: complete once the stream is
+            if verify.flags_dev is None:  # mapped from host memory: complete once the stream is
                 if not synced:
                     torch.cuda.current_stream().synchronize()
-                fired, faults = (int(v) for v in verify[2][:2])
-            elif synced and verify[2] is not None:  # staged (stage_flags) and known complete
-                fired, faults = verify[2].tolist()[:2]
+                fired, faults = (int(v) for v in verify.flags_host[:2])
+            elif synced and stage:  # staged (stage_flags) and known complete
+                fired, faults = stage[0].tolist()[:2]
             else:
-                fired, faults = verify[0].tolist()[:2]
-            if faults:
-                if not was_pass:
-                    raise L.NfdpfError(f"nfdpf_filter_step_tiled: {faults} wave hand-off(s) timed out on the device "
-                                       f"(outputs invalid)")
-                self._pass_fault(faults)  # the one-launch pass's grid was not resident: rerun step by step
-                self.last_verify = "fault"
+                fired, faults = verify.flags_dev.tolist()[:2]
+            if self._faulted(faults, pend.was_pass):
                 return False
-            if fired and not decided:  # (a plan pass: `fired` counts the gates that differ from the plan)
+            if fired and not pend.decided:  # (a plan pass: `fired` counts the gates that differ from the plan)
                 self.last_verify = "fired"
-                if plan is not None:
-                    self._plan = gates_dev.cpu().numpy()  # exact up to its first differing gate
+                if pend.plan is not None:
+                    self._plan = pend.gates.cpu().numpy()  # exact up to its first differing gate
                 return False
-            res.obs_likelihood = verify[1]
+            pend.res.obs_likelihood = verify.obs
             return True
         if shard.world > 1:
-            # ONE all-gather of each rank's summary: its rows' gate terms of every step (the per-row
-            # half of the batch gate's arithmetic, nfdpf_ess_row_terms: T x B floats instead of the
-            # T x B x tiles x 4 doubles of partials), its hand-off fault counter and its per-step
-            # log-weight sums; then the gates over the gathered rows (nfdpf_ess_gate_terms), and
-            # ONE host read of {gates, faults}
-            T = parts.shape[0]
-            stage = pend[11] if len(pend) > 11 else []
+            # ONE all-gather of each rank's summary (_sharded_verify), and ONE host read of {gates, faults}
             if stage:  # staged (stage_flags): read with no stream operation once known complete
                 if not synced:
                     torch.cuda.current_stream().synchronize()
                 host, tot = stage[0], stage[1]
             else:
-                dev_small, tot = self._sharded_verify(parts, tot, shard, N)
+                dev_small, tot = self._sharded_verify(parts, tot, shard, pend.N)
                 host = dev_small.cpu()
-            faults = int(host[T])
-            if faults:
-                if not was_pass:
-                    raise L.NfdpfError(f"nfdpf_filter_step_tiled: {faults} wave hand-off(s) timed out on the device "
-                                       f"(outputs invalid)")
-                self._pass_fault(faults)
-                self.last_verify = "fault"
+            if self._faulted(int(host[-1]), pend.was_pass):
                 return False
-            gates = host[:T].to(torch.int32)
+            gates = host[:-1].to(torch.int32)  # ([T + 1]: the gates, then the faults)
         else:
-            if split_dev is not None:
-                if was_pass:
-                    faults = self._faults_all(shard, split_dev)
-                    if faults:
-                        self._pass_fault(faults)
-                        self.last_verify = "fault"
-                        return False
-                else:
-                    L.check_split_fault("nfdpf_filter_step_tiled", split_dev)
-            gates = ops.ess_gate_tiled_batch(parts, N, 0, False)
-        if plan is not None:  # the pass followed a plan: its actual gates must be the plan's
+            if pend.split_dev is not None:
+                if not pend.was_pass:
+                    L.check_split_fault("nfdpf_filter_step_tiled", pend.split_dev)
+                elif self._faulted(self._faults_all(shard, pend.split_dev), True):
+                    return False
+            gates = ops.ess_gate_tiled_batch(parts, pend.N, 0, False)
+        if pend.plan is not None:  # the pass followed a plan: its actual gates must be the plan's
             g = gates.cpu().numpy()
-            if not np.array_equal(g, plan):
+            if not np.array_equal(g, pend.plan):
                 self.last_verify = "fired"
                 self._plan = g
                 return False
         elif bool(gates.any()):
             self.last_verify = "fired"
             return False
-        res.obs_likelihood = (tot / (shard.B_global * N)).sum().float()
+        pend.res.obs_likelihood = (tot / (shard.B_global * pend.N)).sum().float()
         return True
 
     # -- helpers ----------------------------------------------------------------------------
-    def _pass_fault(self, faults: int):
+    def _pass_fault(self, faults: int, stacklevel: int = 3):
         """A one-launch pass timed out waiting for its own workgroups (its grid was not all
         resident: another process or stream held CUs, or a CU mask): warn, turn the pass off
         for this engine; the caller reruns the pass with the step launches."""
         import warnings
         warnings.warn(f"nfdpf_filter_pass_tiled: {faults} row hand-off wait(s) timed out (the pass's grid was not "
                       f"resident); rerunning with the step launches, the one-launch pass is off for this engine",
-                      RuntimeWarning, stacklevel=3)
+                      RuntimeWarning, stacklevel=stacklevel)
         self.pass_disabled = True
 
     @staticmethod

@@ -23,9 +23,9 @@ ep = mk()
 p = ep.run(*inp, plan=gates, finish=False)
 pend = ep.take_pending()
 torch.cuda.synchronize()
-v = pend[6]
+v = pend.verify
 fl = v[2] if v[0] is None else v[0]
-print("plan pass: flags", [int(x) for x in fl[:3]], "actual gates", pend[10].cpu().tolist())
+print("plan pass: flags", [int(x) for x in fl[:3]], "actual gates", pend.gates.cpu().tolist())
 for f in ("particles", "probs", "index", "lik", "noise", "jac", "prior"):
     a, b = getattr(p, f), getattr(g, f)
     if torch.equal(a, b):
@@ -36,4 +36,4 @@ for f in ("particles", "probs", "index", "lik", "noise", "jac", "prior"):
         print(f, f"differ: first slot {t0}, rows {bad[:, t0].nonzero().flatten().tolist()}, max abs diff at it "
                  f"{float((a - b).reshape(B, T, -1)[:, t0].abs().max()) if a.is_floating_point() else 'idx'}")
 import nfdpf.ops as ops
-parts_p = pend[0]
+parts_p = pend.parts
