@@ -1272,7 +1272,7 @@ __device__ __forceinline__ void pass_encoder(const nfdpf_filter_desc &d, const P
     const float *enc_t = d.enc + ((int64_t)b * d.T + t) * d.E;
     // measure_row_setup (cosine), per wave into its own LDS copy
     const float ve = lane < kE ? enc_t[lane] : 0.f;
-    const double vinv = 1.0 / fmax(sqrt(wave_sum((double)ve * ve)), 1e-12);
+    const double vinv = wave_vinv(ve);
     if (lane < kE) L.encq[we][lane] = ve;
     __builtin_amdgcn_wave_barrier();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");

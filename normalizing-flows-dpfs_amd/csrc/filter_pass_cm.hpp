@@ -239,22 +239,18 @@ __global__ __launch_bounds__(4 * K * 64, 1) void tiled_pass_cm_kernel(const nfdp
     // 2. the measurement of x_t (model/models.py:256-278), unshifted
     float raw = -INFINITY;
     double vinv = 0.0;
-    if constexpr (MEAS == NFDPF_MEAS_COS) {  // measure_row_setup's 1 / max(|v|, 1e-12), per wave
-      const float ve = lane < kE ? d.enc[((int64_t)b * d.T + t) * d.E + lane] : 0.f;
-      vinv = 1.0 / fmax(sqrt(wave_sum((double)ve * ve)), 1e-12);
-    }
+    if constexpr (MEAS == NFDPF_MEAS_COS)  // measure_row_setup's row constant, per wave
+      vinv = wave_vinv(lane < kE ? d.enc[((int64_t)b * d.T + t) * d.E + lane] : 0.f);
     if constexpr (MF) {  // the whole wave: its 64 particles x_t are in xr[t mod K][g]
       const float r = crnvp_lik_mfma(reinterpret_cast<const float *>(wfr), d.n_flows, d.meas_prior_std, L.encq[w],
                                      &L.xr[k][g][0][0]);
       if (valid) raw = r;
     } else if (valid) {
-      if constexpr (MEAS == NFDPF_MEAS_CRNVP) {
-        raw = crnvp_lik(wptr(d.pe_params), wptr(d.meas_params), d.n_flows, d.meas_prior_std, L.encq[w], x0, x1);
-      } else if constexpr (MEAS == NFDPF_MEAS_COS) {  // model/models.py:206-219 (measure<COS>'s arithmetic)
-        double ss, dot;
-        encode_dot<kE>(wptr(d.pe_params), x0, x1, L.encq[w], ss, dot);
-        raw = cos_lik(ss, dot, vinv);
-      } else {  // the gaussian measurement, model/models.py:237-254 (measure<GAUSSIAN>'s arithmetic)
+      if constexpr (MEAS != NFDPF_MEAS_GAUSSIAN) {
+        raw = measure<kE, MEAS>(d, L.encq[w], &vinv, nullptr, x0, x1);
+      } else {
+        // measure<kE, GAUSSIAN>'s arithmetic, restated: called through the shared function this
+        // kernel's register allocation and schedule move
         float e[kE];
         particle_encode<kE>(wptr(d.pe_params), x0, x1, e);
         float m = 0.f;

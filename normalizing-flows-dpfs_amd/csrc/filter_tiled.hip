@@ -1467,7 +1467,7 @@ __device__ __forceinline__ void quad_part(const nfdpf_filter_desc &d, const Tile
     const int lane = threadIdx.x & 63;
     float *encv = encq[w - 8];
     const float ve = lane < kE ? S.enc[lane] : 0.f;
-    const double vinv = 1.0 / fmax(sqrt(wave_sum((double)ve * ve)), 1e-12);
+    const double vinv = wave_vinv(ve);
     if (lane < kE) encv[lane] = ve;
     __builtin_amdgcn_wave_barrier();
     asm volatile("" ::: "memory");

@@ -2,7 +2,7 @@
 // gaussian measurement kernels are built for, forward and backward.  A further width is one
 // more X(...) entry here (even, <= 64: the backward kernels hold a row's encoding in one wave).
 // The tuned step and pass kernels stay at kE (measure.hpp); the other widths run the standalone
-// kernels of measure_wide.hip and the width-templated backwards.
+// kernel of measure.hip (the same measure<E, MEAS>) and the width-templated backwards.
 #pragma once
 
 #include <type_traits>

@@ -1,5 +1,7 @@
-// measure.hpp -- per-particle measurement models (model/models.py:206-278) and the per-row
-// shared state of the fused filter step.
+// measure.hpp -- THE per-particle measurement models (model/models.py:206-278), templated on the
+// frame-encoding width E, and the per-row shared state of the fused filter step.  The tuned
+// step and pass kernels instantiate them at kE; the standalone kernel of measure.hip at every
+// width of meas_widths.hpp.
 #pragma once
 
 #include "flows.hpp"
@@ -41,13 +43,13 @@ struct MeasArgs {
 // condition = the particle encoding; N(0, prior_std^2 I) prior + log-det.  pe / mp: the encoder
 // and flow blobs behind constant-address-space pointers (scalar loads) or plain pointers into
 // LDS (tiled_prop_kernel stages them per workgroup) -- the same arithmetic either way.
-template <class WF>
+template <int E, class WF>
 __device__ __forceinline__ float crnvp_lik(WF pe, WF mp, int n_flows, float prior_std, const float *encv,
                                            float x0, float x1) {
-  float e[kE];
-  particle_encode<kE>(pe, x0, x1, e);
-  constexpr int HALF = kE / 2;
-  constexpr int ns = net_size<HALF, kH>(kE);
+  float e[E];
+  particle_encode<E>(pe, x0, x1, e);
+  constexpr int HALF = E / 2;
+  constexpr int ns = net_size<HALF, kH>(E);
   float lo[HALF], up[HALF];
 #pragma unroll
   for (int k = 0; k < HALF; ++k) {
@@ -61,8 +63,8 @@ __device__ __forceinline__ float crnvp_lik(WF pe, WF mp, int n_flows, float prio
 #pragma unroll
     for (int n = 0; n < 2; ++n)
 #pragma unroll
-      for (int j = 0; j < kH; ++j) cb[n * kH + j] = fold_pair_c<HALF, kH, kE>(fw + n * ns, j, e);
-    ld += coupling_forward<HALF, kH>(fw, kE, lo, up, cb);
+      for (int j = 0; j < kH; ++j) cb[n * kH + j] = fold_pair_c<HALF, kH, E>(fw + n * ns, j, e);
+    ld += coupling_forward<HALF, kH>(fw, E, lo, up, cb);
   }
   // the prior's quadratic form in fp64 (32 terms of ~10 each: fp32 lost ~1e-4 absolute)
   const double is = 1.0 / (double)prior_std;
@@ -73,49 +75,52 @@ __device__ __forceinline__ float crnvp_lik(WF pe, WF mp, int n_flows, float prio
     m = fma(a, a, m);
     m = fma(c, c, m);
   }
-  const double lp = -0.5 * (kE * 1.8378770664093453 + m) - kE * log((double)prior_std);
+  const double lp = -0.5 * (E * 1.8378770664093453 + m) - E * log((double)prior_std);
   return (float)(lp + (double)ld);
 }
 
-template <int MEAS>
-__device__ __forceinline__ float measure(const MeasArgs &d, const StepShared &L, float x0,
-                                         float x1) {
+// one particle's raw likelihood at frame-encoding width E from the row constants of
+// measure_row_setup: encv, vinv (cos only) and nnrow (NN only; the others may pass nullptr).
+// d: MeasArgs, or the filter descriptor itself (the same four members)
+template <int E, int MEAS, class Args>
+__device__ __forceinline__ float measure(const Args &d, const float *encv, const double *vinv, const float *nnrow,
+                                         float x0, float x1) {
   if constexpr (MEAS == NFDPF_MEAS_COS) {
     // measurement_model_cosine_distance + et_distance (model/models.py:206-219, utils.py:8-15)
     // <e/|e|, v/|v|> computed as <e, v>/(|e| |v|) in fp64 (flows.hpp cos_lik)
     double ss, dot;
-    encode_dot<kE>(wptr(d.pe_params), x0, x1, L.encv, ss, dot);
-    return cos_lik(ss, dot, L.vinv);
+    encode_dot<E>(wptr(d.pe_params), x0, x1, encv, ss, dot);
+    return cos_lik(ss, dot, *vinv);
   } else if constexpr (MEAS == NFDPF_MEAS_CRNVP) {
-    return crnvp_lik(wptr(d.pe_params), wptr(d.meas_params), d.n_flows, d.meas_prior_std, L.encv, x0, x1);
+    return crnvp_lik<E>(wptr(d.pe_params), wptr(d.meas_params), d.n_flows, d.meas_prior_std, encv, x0, x1);
   } else if constexpr (MEAS == NFDPF_MEAS_GAUSSIAN) {
     // measurement_model_Gaussian with N(1, 100 I) (DPFs.py:84-86, model/models.py:237-254)
-    float e[kE];
-    particle_encode<kE>(wptr(d.pe_params), x0, x1, e);
+    float e[E];
+    particle_encode<E>(wptr(d.pe_params), x0, x1, e);
     float m = 0.f;
 #pragma unroll
-    for (int j = 0; j < kE; ++j) {
-      const float v = (L.encv[j] - e[j] - 1.0f) * 0.1f;
+    for (int j = 0; j < E; ++j) {
+      const float v = (encv[j] - e[j] - 1.0f) * 0.1f;
       m = fmaf(v, v, m);
     }
-    return -0.5f * (kE * 1.8378770664093453f + m) - kE * 2.302585092994046f;
+    return -0.5f * (E * 1.8378770664093453f + m) - E * 2.302585092994046f;
   } else if constexpr (MEAS == NFDPF_MEAS_NN) {
     // measurement_model_NN (model/models.py:221-235): sigmoid(MLP([enc_obs, enc_particle])).log()
-    float e[kE];
-    particle_encode<kE>(wptr(d.pe_params), x0, x1, e);
+    float e[E];
+    particle_encode<E>(wptr(d.pe_params), x0, x1, e);
     // W1 [64, 2E] and W2 [64, 64] in row_pairs layout, W3 [1, 64] and biases plain
     cfloat *P = wptr(d.meas_params);
     cf2 *W1 = (cf2 *)P;
     f2 h[kNnH / 2];
 #pragma unroll
     for (int m = 0; m < kNnH / 2; ++m) {
-      f2 a = f2{L.nnrow[2 * m], L.nnrow[2 * m + 1]};
+      f2 a = f2{nnrow[2 * m], nnrow[2 * m + 1]};
 #pragma unroll
-      for (int k = 0; k < kE; ++k) a = pfma(W1[m * 2 * kE + kE + k], splat(e[k]), a);
+      for (int k = 0; k < E; ++k) a = pfma(W1[m * 2 * E + E + k], splat(e[k]), a);
       h[m] = relu2(a);
     }
-    cf2 *W2 = (cf2 *)(P + kNnH * 2 * kE + kNnH), *b2 = (cf2 *)(P + kNnH * 2 * kE + kNnH + kNnH * kNnH);
-    cfloat *W3 = P + kNnH * 2 * kE + kNnH + kNnH * kNnH + kNnH, *b3 = W3 + kNnH;
+    cf2 *W2 = (cf2 *)(P + kNnH * 2 * E + kNnH), *b2 = (cf2 *)(P + kNnH * 2 * E + kNnH + kNnH * kNnH);
+    cfloat *W3 = P + kNnH * 2 * E + kNnH + kNnH * kNnH + kNnH, *b3 = W3 + kNnH;
     float o = b3[0];
     for (int m = 0; m < kNnH / 2; ++m) {
       f2 a = b2[m];
@@ -130,27 +135,38 @@ __device__ __forceinline__ float measure(const MeasArgs &d, const StepShared &L,
   }
 }
 
-
-// per-row constants of the measurement (frame encoding, NN obs-half fold); all threads call
 template <int MEAS>
-__device__ __forceinline__ void measure_row_setup(const float *enc, const float *meas_params,
-                                                  StepShared &L) {
+__device__ __forceinline__ float measure(const MeasArgs &d, const StepShared &L, float x0, float x1) {
+  return measure<kE, MEAS>(d, L.encv, &L.vinv, L.nnrow, x0, x1);
+}
+
+// cos: 1 / max(|v|, 1e-12) in fp64 of the row's frame encoding, one element v per lane of a
+// whole wave (0 past the width)
+__device__ __forceinline__ double wave_vinv(float v) {
+  return 1.0 / fmax(sqrt(wave_sum((double)v * v)), 1e-12);
+}
+
+// per-row constants of the measurement (frame encoding, NN obs-half fold) into L.encv, L.vinv
+// and L.nnrow of the kernel's row struct (StepShared, measure.hip's MeasRow<E>); all threads call
+template <int MEAS, int E = kE, class Row>
+__device__ __forceinline__ void measure_row_setup(const float *enc, const float *meas_params, Row &L) {
+  static_assert(E <= 64 && E % 2 == 0, "one wave holds the row's frame encoding");
   const int tid = threadIdx.x;
   if (tid < 64) {
-    const float v = tid < kE ? enc[tid] : 0.f;
+    const float v = tid < E ? enc[tid] : 0.f;
     if (MEAS == NFDPF_MEAS_COS) {
-      const double nrm = sqrt(wave_sum((double)v * v));
-      if (tid < kE) L.encv[tid] = v;
-      if (tid == 0) L.vinv = 1.0 / fmax(nrm, 1e-12);
-    } else if (tid < kE) {
+      const double vi = wave_vinv(v);
+      if (tid < E) L.encv[tid] = v;
+      if (tid == 0) L.vinv = vi;
+    } else if (tid < E) {
       L.encv[tid] = v;
     }
   }
   if (MEAS == NFDPF_MEAS_NN && tid < kNnH) {
     // obs half of likelihood_est's first layer (row_pairs layout: [m][k][2], m = tid / 2)
-    float a = meas_params[kNnH * 2 * kE + tid];
-    const float *w = meas_params + (tid >> 1) * 2 * kE * 2 + (tid & 1);
-    for (int k = 0; k < kE; ++k) a = fmaf(w[2 * k], enc[k], a);
+    float a = meas_params[kNnH * 2 * E + tid];
+    const float *w = meas_params + (tid >> 1) * 2 * E * 2 + (tid & 1);
+    for (int k = 0; k < E; ++k) a = fmaf(w[2 * k], enc[k], a);
     L.nnrow[tid] = a;
   }
 }

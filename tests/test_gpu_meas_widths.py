@@ -1,5 +1,5 @@
 """Frame-encoding widths 16 and 64 (--hiddensize) of the cos / CRNVP / NN / gaussian measurements
-on the HIP kernels (csrc/measure_wide.hip, the width-templated backwards of measure_bwd.hip /
+on the HIP kernels (csrc/measure.hip, the width-templated backwards of measure_bwd.hip /
 nn_bwd.hip, nfdpf_cond_stack[_backward] at dim 16 / 64): kernel, module, FilterEngine and
 DPF(args).  GPU box only.
 
@@ -380,6 +380,35 @@ def test_engine_tiled_vs_oracle(name, E):
 def test_engine_fused_vs_oracle(name):
     """The same through the one-workgroup-per-row step kernel (kernel="fused") at E = 64."""
     _run_engine_case(name, 64, "fused")
+
+
+@pytest.mark.parametrize("kind", ["cos", "NN"])
+def test_step_likelihood_equals_standalone_at_32(kind):
+    """The step kernels and the standalone kernel instantiate one measure<E, MEAS> (csrc/measure.hpp)
+    at E = 32: the likelihood history of FilterEngine's step launches (kernel="tiled", the one-launch
+    pass off, device RNG; B = 2, N = 300 -- two tiles, the second partial -- T = 2) against
+    ops.measurement on the same encodings and the history's own particles.  cos and NN: phase 2
+    applies no row-max shift to them, so the history holds the raw value."""
+    from nfdpf import ops
+    from nfdpf.engine import FilterConfig, FilterEngine
+    E, B, N, T = 32, 2, 300, 2
+    mods = _Mods(E, seed=2000)
+    g = torch.Generator().manual_seed(21)
+    state = torch.cat([torch.randn(B, T, 2, generator=g) * 20, torch.randn(B, T, 2, generator=g) * 3], -1)
+    with torch.no_grad():  # "aligned" frame encodings, as _run_engine_case
+        enc = mods.particle_encoder(state[..., :2])
+        enc = (enc * (1 + 0.3 * torch.randn(enc.shape, generator=g))).to(DEV)
+    pe, mb = _blobs(mods, kind)
+    eng = FilterEngine(FilterConfig(N=N, measurement=kind, resampler="soft", kernel="tiled", seed=5), mods.to(DEV))
+    eng.pass_disabled = True  # the step launches
+    out = eng.run(enc, state[:, 0].to(DEV), state[..., 2:].contiguous().to(DEV))
+    torch.cuda.synchronize()
+    assert not eng.last_pass and torch.isfinite(out.lik).all()
+    for t_ in range(T):
+        lik = ops.measurement(kind, pe, mb, 2, enc[:, t_].contiguous(), out.particles[:, t_].contiguous(), 2.5)
+        print(f"{kind} t={t_}: max |step - standalone| {float((out.lik[:, t_] - lik).abs().max()):.3e}, "
+              f"max |lik| {float(lik.abs().max()):.3e}")
+        assert torch.equal(out.lik[:, t_], lik), f"{kind}, step {t_}"
 
 
 def _dpf(meas, H=64, B=2, N=50, T=3):
