@@ -48,8 +48,8 @@
 //
 // Reductions have a fixed order (deterministic): A / B = per chain wave DPP sums, the row
 // total over (tile, wave) in order -- the order of the three-launch tiled path (tiled_front_kernel
-// -> store_sums4, block_sum_roles_store -> tiled_ctx); the tile's softmax partial = the quad
-// launch's merge over encoder waves 8..15.
+// -> block_sum4_store, block_sum_roles_store -> tiled_ctx); the tile's softmax partial = the quad
+// launch's merge over encoder waves 8..15 (softmax_merge_waves's arithmetic, filter_tiled.hip).
 
 namespace nfdpf {
 

@@ -160,10 +160,7 @@ __device__ __forceinline__ float pass_cm_norm(const nfdpf_filter_desc &d, const 
     d.hist_p[o] = p;
     d.hist_lik[o] = lk;
     lp = logf(p);
-    sf[0] = (double)p * p;
-    sf[1] = (double)p * L.nb[par][3][slot];
-    sf[2] = (double)p * L.nb[par][4][slot];
-    sf[3] = lw;
+    fin_terms(p, L.nb[par][3][slot], L.nb[par][4][slot], lw, sf);
   }
   wave_sum_dpp_n(sf);
   const int lane = threadIdx.x & 63, tiles = n_tiles(d.N);

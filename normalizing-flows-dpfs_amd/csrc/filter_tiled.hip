@@ -262,6 +262,17 @@ __device__ __forceinline__ float prev_p_of(const PrevIn &v, const RowNorm &rn, b
   lw = ((v.lr + lk) + v.prior) - v.prop;
   return expf(lw - rn.shift) / rn.Ssum + 1e-12f;
 }
+// A particle's terms of its slot's fin sums: p^2, p x0, p x1, logw.
+// (The three lines before each call -- prev_p_of, then hlik / hp stored -- stay at the call sites:
+// folded into this helper they were tried by value, by reference and through pointers, and each time
+// tiled_dyn_kernel<false> / <true> moved 691 / 696 lines of schedule at 85 / 46 VGPRs unchanged,
+// launches no benchmark line runs.)
+__device__ __forceinline__ void fin_terms(float p, float x0, float x1, float lw, double (&sf)[4]) {
+  sf[0] = (double)p * p;
+  sf[1] = (double)p * x0;
+  sf[2] = (double)p * x1;
+  sf[3] = lw;
+}
 // row b's softmax partials inside ess_all (global rows when the batch is sharded)
 // row of ess_all holding local row b: the global row of a sharded batch, unless the
 // speculative-gate mode keeps only this shard's rows (ess_local)
@@ -282,6 +293,8 @@ __device__ __forceinline__ void finish_prev(const nfdpf_filter_desc &d, TiledWs 
   const bool shifted = shifted_meas(d.measurement);
   const RowNorm rn = row_norm(prev_sm(d, b, tiles), tiles, shifted);
   const RowSlot Sp = row_slot(d, b, d.t - 1);
+  // (its own four sums, not fin_terms: through an array the C3 step launch's epilogue moved and that
+  // line measured 2.642-2.660e9 against the parent's 2.646-2.677e9, profiles/fold_prop_launches_ab.jsonl)
   double sp2 = 0, px = 0, py = 0, sw = 0;
   if (own && i < d.N) {
     float lw, lk;
@@ -308,11 +321,6 @@ __device__ __forceinline__ Ctx4 tiled_ctx(const double *st, int b, int tiles, in
     b1 += p[4 * k + 3];
   }
   return ctx_from_sums(a0, a1, b0, b1, N);
-}
-
-__device__ __forceinline__ void store_sums4(double *dst, double a, double b, double c, double e,
-                                            double *sh) {
-  block_sum4_store(a, b, c, e, sh, dst);
 }
 
 // ---- K1: ESS gate + resampling + motion, per (tile, row).  The gate (DPFs.py:163-165) is
@@ -520,7 +528,7 @@ __global__ __launch_bounds__(kTile) void tiled_front_kernel(const nfdpf_filter_d
     const FoldRef r = fold_ref(d.cond_params, net_size<1, kH>(d.E + 4), threadIdx.x);
     ws.cb_cond[b * kCb + threadIdx.x] = fold_acc(r, d.E + 4, fold_bias0(r, d.E + 4), S.enc, 0, d.E);
   }
-  store_sums4(ws.st_phys + ((int64_t)b * tiles + tile) * 4, s0, s1, q0, q1, shd);
+  block_sum4_store(s0, s1, q0, q1, shd, ws.st_phys + ((int64_t)b * tiles + tile) * 4);
 }
 
 // (The fused step -- the merged front launch and the quad proposal launch as ONE launch per
@@ -625,10 +633,7 @@ __global__ __launch_bounds__(SPLIT ? 2 * kTile : kTile) void tiled_dyn_kernel(co
       const float p = prev_p_of(pv, rn, shifted, lw, lk);
       if (shifted) Sp.hlik[i] = lk;
       Sp.hp[i] = p;
-      sf[0] = (double)p * p;
-      sf[1] = (double)p * pv.x0;
-      sf[2] = (double)p * pv.x1;
-      sf[3] = lw;
+      fin_terms(p, pv.x0, pv.x1, lw, sf);
     }
   }
   double *dst = ws.st_dyn + ((int64_t)b * tiles + tile) * 4;
@@ -638,7 +643,7 @@ __global__ __launch_bounds__(SPLIT ? 2 * kTile : kTile) void tiled_dyn_kernel(co
   else if (defer)
     block_sum8_store(sd, dst, sf, dfin, shd);
   else
-    store_sums4(dst, sd[0], sd[1], sd[2], sd[3], shd);
+    block_sum4_store(sd[0], sd[1], sd[2], sd[3], shd, dst);
 }
 
 // ---- K1+K2 merged (the split-net path of --NF-dyn RealNVP with --NF-cond and the cosine
@@ -954,45 +959,75 @@ __global__ __launch_bounds__(2 * kTile) void tiled_fdyn_kernel(const nfdpf_filte
   fdyn_part(d, ws);
 }
 
-// softmax partials of the unshifted log-weight u over this tile
-__device__ __forceinline__ void store_softmax(float u, bool valid, double *sm, float *shf, double *shd) {
-  // per wave (max, sum e^(u - max), sum e^(2(u - max))), merged over the waves with one
-  // barrier into this tile's {max, sum, sum of squares} (sm[0..2])
+// ---- The tile's softmax partials of the unshifted log-weight u, {max u, sum e^(u - max),
+// sum e^(2(u - max))}: each wave's own partials (softmax_wave_terms, its two wave sums,
+// softmax_wave_put), one barrier, then thread 0 rescales the waves' sums to the tile's max and
+// adds them in wave order (softmax_merge_waves).  The ESS gate reads these partials, so the
+// proposal launches form them with these helpers (store_softmax_rel: with its own copy of the
+// same lines): the same operations in the same order.
+
+// this wave's max of u over its valid lanes; ev = the lane's e^(u - max), 0 on an invalid lane
+__device__ __forceinline__ float softmax_wave_terms(float u, bool valid, float &ev) {
   const float mw = wave_max_dpp(valid ? u : -INFINITY);
-  const float ev = valid ? expf(u - mw) : 0.f;
-  const double ew = wave_sum_dpp((double)ev);
-  const double qw = wave_sum_dpp((double)ev * ev);
+  ev = valid ? expf(u - mw) : 0.f;
+  return mw;
+}
+// the wave's first lane leaves (max, sum ev, sum ev^2) in shf[w], shd[2 w], shd[2 w + 1]
+__device__ __forceinline__ void softmax_wave_put(float mw, double ew, double qw, float *shf, double *shd) {
   const int w = threadIdx.x >> 6;
   if ((threadIdx.x & 63) == 0) {
     shf[w] = mw;
     shd[2 * w] = ew;
     shd[2 * w + 1] = qw;
   }
+}
+__device__ __forceinline__ void softmax_wave_partials(float u, bool valid, float *shf, double *shd) {
+  float ev;
+  const float mw = softmax_wave_terms(u, valid, ev);
+  const double ew = wave_sum_dpp((double)ev);
+  const double qw = wave_sum_dpp((double)ev * ev);
+  softmax_wave_put(mw, ew, qw, shf, shd);
+}
+// thread 0, after the barrier: the partials of the nw waves (a wave without a valid lane holds
+// max = -inf and is skipped) relative to the tile's max m -> sm[0] = m_out (max u as the partials
+// carry it), sm[1], sm[2]
+__device__ __forceinline__ void softmax_merge_waves(int nw, float m, double m_out, const float *shf,
+                                                    const double *shd, double *sm) {
+  double sum = 0.0, sq = 0.0;
+  for (int k = 0; k < nw; ++k)
+    if (shf[k] > -INFINITY) {
+      const double f = (double)expf(shf[k] - m);
+      sum += shd[2 * k] * f;
+      sq += shd[2 * k + 1] * f * f;
+    }
+  sm[0] = m_out;
+  sm[1] = sum;
+  sm[2] = sq;
+}
+
+// softmax partials of the unshifted log-weight u over this tile -> sm[0..2]
+__device__ __forceinline__ void store_softmax(float u, bool valid, double *sm, float *shf, double *shd) {
+  softmax_wave_partials(u, valid, shf, shd);
   __syncthreads();
   if (threadIdx.x == 0) {
     const int nw = (blockDim.x + 63) >> 6;
     float m = shf[0];
     for (int k = 1; k < nw; ++k) m = fmaxf(m, shf[k]);
-    double sum = 0.0, sq = 0.0;
-    for (int k = 0; k < nw; ++k)
-      if (shf[k] > -INFINITY) {
-        const double f = (double)expf(shf[k] - m);
-        sum += shd[2 * k] * f;
-        sq += shd[2 * k + 1] * f * f;
-      }
-    sm[0] = m;
-    sm[1] = sum;
-    sm[2] = sq;
+    softmax_merge_waves(nw, m, m, shf, shd, sm);
   }
 }
 
 // store_softmax for a shifted measurement whose raw likelihood may be large (CRNVP: ~1e3 at
 // trained weights): u is the log-weight with the likelihood taken relative to lmw, the wave's max
-// raw likelihood (so nothing is rounded at the raw likelihood's magnitude); the waves merge
-// relative to the tile's max raw likelihood lm (-> sm[3]) and sm[0] = max u in fp64, m + lm
-// (tiled_pass_cm_kernel's pass_cm_poll_c, the same arithmetic).  shd >= 24 doubles.
+// raw likelihood (so nothing is rounded at the raw likelihood's magnitude); thread 0 rebases each
+// wave's max to the tile's max raw likelihood lm (-> sm[3]) before softmax_merge_waves' loop, and
+// sm[0] = max u in fp64, m + lm (as tiled_pass_cm_kernel's pass_cm_poll_c forms it from its
+// exchange granules).  shd >= 24 doubles.
 __device__ __forceinline__ void store_softmax_rel(float u, bool valid, float lmw, double *sm, float *shf,
                                                   double *shd) {
+  // (its own copy of softmax_wave_partials and of softmax_merge_waves' loop: built from the helpers
+  // the C3 step launch's epilogue moved -- 26 lines, 121 VGPRs unchanged -- and that line measured
+  // 2.642-2.660e9 against the parent's 2.646-2.677e9, profiles/fold_prop_launches_ab.jsonl)
   const float mw = wave_max_dpp(valid ? u : -INFINITY);
   const float ev = valid ? expf(u - mw) : 0.f;
   const double ew = wave_sum_dpp((double)ev);
@@ -1028,47 +1063,23 @@ __device__ __forceinline__ void store_softmax_rel(float u, bool valid, float lmw
   }
 }
 
-// store_softmax (role-0 lanes carry u) plus, with the same barrier, the four deferred-
-// normalisation sums of the role-1 waves (block_sum_roles_store's order) into fin.
-// smd >= 48 doubles.
-__device__ __forceinline__ void store_softmax_fin(float u, bool valid, double *sm, const double (&sf)[4],
-                                                  double *fin, float *shf, double *shd) {
-  const float mw = wave_max_dpp(valid ? u : -INFINITY);
-  const float ev = valid ? expf(u - mw) : 0.f;
-  const double ew = wave_sum_dpp((double)ev);
-  const double qw = wave_sum_dpp((double)ev * ev);
-  double f4[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) f4[k] = wave_sum_dpp(sf[k]);
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-    shf[w] = mw;
-    shd[2 * w] = ew;
-    shd[2 * w + 1] = qw;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) shd[16 + 4 * w + k] = f4[k];
-  }
-  __syncthreads();
-  const int nw = (blockDim.x + 63) >> 6;
-  if (threadIdx.x == 0) {
-    float m = shf[0];
-    for (int k = 1; k < nw; ++k) m = fmaxf(m, shf[k]);
-    double sum = 0.0, sq = 0.0;
-    for (int k = 0; k < nw; ++k)
-      if (shf[k] > -INFINITY) {
-        const double f = (double)expf(shf[k] - m);
-        sum += shd[2 * k] * f;
-        sq += shd[2 * k + 1] * f * f;
-      }
-    sm[0] = m;
-    sm[1] = sum;
-    sm[2] = sq;
-  } else if (threadIdx.x >= 64 && threadIdx.x < 68) {  // role-1 waves 1, 3, 5, 7 in order
-    const int k = threadIdx.x - 64;
-    double a = shd[16 + 4 * 1 + k];
-    for (int q = 1; q < 4; ++q) a += shd[16 + 4 * (2 * q + 1) + k];
-    fin[k] = a;
-  }
+// The K3 launches finish the proposal fold here, for fold lane k (< n_flows * 4 * kH): the encoding
+// columns came from K1 (ws.cb_cond), add [mean, std] of the row's proposal context (the partial
+// sums st) -> L.cb_cond, in split order (split_cb_index) for the wave-pair launches.
+// (K: the callers' own index type -- unsigned threadIdx.x or int -- so the addresses extend as they did)
+template <bool SPLIT, class K>
+__device__ __forceinline__ void prop_fold_to_lds(const nfdpf_filter_desc &d, const TiledWs &ws, StepShared &L, int b,
+                                                 int tiles, K k, const double *st) {
+  const Ctx4 cp = tiled_ctx(st, b, tiles, d.N);
+  const float c4[4] = {cp.m0, cp.m1, cp.s0, cp.s1};
+  const FoldRef r = fold_ref(d.cond_params, net_size<1, kH>(d.E + 4), k);
+  reinterpret_cast<float *>(L.cb_cond)[SPLIT ? split_cb_index(k) : k] =
+      fold_acc(r, d.E + 4, ws.cb_cond[b * kCb + k], c4, d.E, d.E + 4);
+}
+// ... and entry k of the row's folded nf_dyn biases (K2 left them in ws.cb_dyn) -> L.cb_dyn
+template <bool SPLIT>
+__device__ __forceinline__ void cb_dyn_to_lds(const TiledWs &ws, StepShared &L, int b, unsigned k) {
+  reinterpret_cast<float *>(L.cb_dyn)[SPLIT ? split_cb_index(k) : k] = ws.cb_dyn[b * kCb + k];
 }
 
 // ---- K3: proposal + measurement
@@ -1104,16 +1115,8 @@ __global__ __launch_bounds__(kTile) void tiled_prop_kernel(const nfdpf_filter_de
   }
   if (MEAS != NFDPF_MEAS_EXTERNAL) measure_row_setup<MEAS>(S.enc, d.meas_params, L);
   const int ncb = d.n_flows * 4 * kH;
-  if (NFD && threadIdx.x < ncb)
-    reinterpret_cast<float *>(L.cb_dyn)[threadIdx.x] = ws.cb_dyn[b * kCb + threadIdx.x];
-  if (NFC && threadIdx.x < ncb) {
-    // finish the proposal fold: the encoding columns came from K1, add [mean, std] of x_dyn
-    const Ctx4 cp = tiled_ctx(NFD ? ws.st_dyn : ws.st_phys, b, tiles, d.N);
-    const float c4[4] = {cp.m0, cp.m1, cp.s0, cp.s1};
-    const FoldRef r = fold_ref(d.cond_params, net_size<1, kH>(d.E + 4), threadIdx.x);
-    reinterpret_cast<float *>(L.cb_cond)[threadIdx.x] =
-        fold_acc(r, d.E + 4, ws.cb_cond[b * kCb + threadIdx.x], c4, d.E, d.E + 4);
-  }
+  if (NFD && threadIdx.x < ncb) cb_dyn_to_lds<false>(ws, L, b, threadIdx.x);
+  if (NFC && threadIdx.x < ncb) prop_fold_to_lds<false>(d, ws, L, b, tiles, threadIdx.x, NFD ? ws.st_dyn : ws.st_phys);
   __syncthreads();
   if (!NFD && d.defer_norm && d.t > 0)  // no K2 in this config
     finish_prev(d, ws, b, tile, i, true, i < d.N ? load_prev_in(row_slot(d, b, d.t - 1), i) : PrevIn{}, L.d);
@@ -1162,15 +1165,12 @@ __global__ __launch_bounds__(kTile) void tiled_prop_kernel(const nfdpf_filter_de
 // the nf_dyn forward and densities while the measurement waves evaluate the likelihood of the
 // same particles -- two independent chains per SIMD instead of one, at a batch size where one
 // wave per SIMD is all the particles there are.
-// With the cosine measurement a third role splits the encoder's output layer: waves 4-7 and
-// 8-11 each produce half of the 32 outputs and their partial (|e|^2, <e, v>).
-template <bool NFD, bool NFC, int MEAS, int ROLES>
-__global__ __launch_bounds__(ROLES * kTile) void tiled_prop2_kernel(const nfdpf_filter_desc d, TiledWs ws) {
+template <bool NFD, bool NFC, int MEAS>
+__global__ __launch_bounds__(2 * kTile) void tiled_prop2_kernel(const nfdpf_filter_desc d, TiledWs ws) {
   __shared__ StepShared L;
   __shared__ float qx[kTile][2];
   __shared__ float lx[kTile];
-  __shared__ double ssx[ROLES][kTile], dotx[ROLES][kTile];
-  __shared__ float smf[16];   // per-wave softmax partials (up to 12 waves)
+  __shared__ float smf[16];   // per-wave softmax partials
   __shared__ double smd[48];
   const int tiles = n_tiles(d.N);
   int b, tile;
@@ -1188,16 +1188,9 @@ __global__ __launch_bounds__(ROLES * kTile) void tiled_prop2_kernel(const nfdpf_
   }
   measure_row_setup<MEAS>(S.enc, d.meas_params, L);
   const int ncb = d.n_flows * 4 * kH;
-  if (NFD && threadIdx.x < ncb)
-    reinterpret_cast<float *>(L.cb_dyn)[threadIdx.x] = ws.cb_dyn[b * kCb + threadIdx.x];
-  if (threadIdx.x >= kTile && threadIdx.x - kTile < ncb) {
-    // finish the proposal fold: the encoding columns came from K1, add [mean, std] of x_dyn
-    const int k = threadIdx.x - kTile;
-    const Ctx4 cp = tiled_ctx(NFD ? ws.st_dyn : ws.st_phys, b, tiles, d.N);
-    const float c4[4] = {cp.m0, cp.m1, cp.s0, cp.s1};
-    const FoldRef r = fold_ref(d.cond_params, net_size<1, kH>(d.E + 4), k);
-    reinterpret_cast<float *>(L.cb_cond)[k] = fold_acc(r, d.E + 4, ws.cb_cond[b * kCb + k], c4, d.E, d.E + 4);
-  }
+  if (NFD && threadIdx.x < ncb) cb_dyn_to_lds<false>(ws, L, b, threadIdx.x);
+  if (threadIdx.x >= kTile && threadIdx.x - kTile < ncb)
+    prop_fold_to_lds<false>(d, ws, L, b, tiles, (int)(threadIdx.x - kTile), NFD ? ws.st_dyn : ws.st_phys);
   __syncthreads();
   if (!NFD && d.defer_norm && d.t > 0)  // no K2 in this config
     finish_prev(d, ws, b, tile, i, flows, flows && i < d.N ? load_prev_in(row_slot(d, b, d.t - 1), i) : PrevIn{},
@@ -1210,18 +1203,9 @@ __global__ __launch_bounds__(ROLES * kTile) void tiled_prop2_kernel(const nfdpf_
   }
   __syncthreads();
   float lk = -INFINITY, u = 0.f, propose = 0.f, prior = 0.f;
-  const int role = threadIdx.x / kTile;
   if (valid) {
     if (flows) {
       stage_prior<NFD, NFC>(d, S, i, in, L.cb_dyn, q0x, q1x, jp, propose, prior);
-    } else if (ROLES == 3) {
-      // cosine measurement, half of the encoder outputs per role (model/models.py:206-219)
-      static_assert(ROLES != 3 || MEAS == NFDPF_MEAS_COS, "three roles: cosine measurement only");
-      constexpr int HP = kE / 4;  // output pairs per role
-      double ss, dot;
-      encode_dot<kE, HP>(wptr(d.pe_params), qx[pl][0], qx[pl][1], L.encv, ss, dot, (role - 1) * HP);
-      ssx[role][pl] = ss;
-      dotx[role][pl] = dot;
     } else {
       lk = stage_measure<MEAS>(d, L, qx[pl][0], qx[pl][1]);
       S.hlik[i] = lk;
@@ -1229,16 +1213,7 @@ __global__ __launch_bounds__(ROLES * kTile) void tiled_prop2_kernel(const nfdpf_
     }
   }
   __syncthreads();
-  if (flows && valid) {
-    float lik;
-    if constexpr (ROLES == 3) {
-      lik = cos_lik(ssx[1][pl] + ssx[2][pl], dotx[1][pl] + dotx[2][pl], L.vinv);
-      S.hlik[i] = lik;
-    } else {
-      lik = lx[pl];
-    }
-    u = logw(lr, lik, prior, propose);
-  }
+  if (flows && valid) u = logw(lr, lx[pl], prior, propose);
   double *sm = reinterpret_cast<double *>(d.ess_out) + ((int64_t)b * tiles + tile) * kSm;
   // the measurement waves hold lk, the others -inf
   const float lm = meas_shifted<MEAS>() ? block_max_dpp(lk, L.f) : 0.f;
@@ -1283,17 +1258,9 @@ __global__ __launch_bounds__(2 * kTile) void tiled_prop_split_kernel(const nfdpf
   if (threadIdx.x < 16) xflag[threadIdx.x] = 0;
   pair_clear(xbuf, kTile);
   const int ncb = d.n_flows * 4 * kH;
-  if (threadIdx.x < ncb)
-    reinterpret_cast<float *>(L.cb_dyn)[split_cb_index(threadIdx.x)] = ws.cb_dyn[b * kCb + threadIdx.x];
-  if (threadIdx.x >= kTile && threadIdx.x - kTile < ncb) {
-    // finish the proposal fold: the encoding columns came from K1, add [mean, std] of x_dyn
-    const int k = threadIdx.x - kTile;
-    const Ctx4 cp = tiled_ctx(ws.st_dyn, b, tiles, d.N);
-    const float c4[4] = {cp.m0, cp.m1, cp.s0, cp.s1};
-    const FoldRef r = fold_ref(d.cond_params, net_size<1, kH>(d.E + 4), k);
-    reinterpret_cast<float *>(L.cb_cond)[split_cb_index(k)] =
-        fold_acc(r, d.E + 4, ws.cb_cond[b * kCb + k], c4, d.E, d.E + 4);
-  }
+  if (threadIdx.x < ncb) cb_dyn_to_lds<true>(ws, L, b, threadIdx.x);
+  if (threadIdx.x >= kTile && threadIdx.x - kTile < ncb)
+    prop_fold_to_lds<true>(d, ws, L, b, tiles, (int)(threadIdx.x - kTile), ws.st_dyn);
   __syncthreads();
   PairX x = pair_of(xbuf, xflag, role, slot);
   float u = 0.f;
@@ -1332,33 +1299,21 @@ __device__ __forceinline__ void wave_partials_quad(float u, bool valid, bool car
     if ((threadIdx.x & 63) == 0) shf[w] = -INFINITY;
     return;
   }
-  const float mw = wave_max_dpp(valid ? u : -INFINITY);
-  const float ev = valid ? expf(u - mw) : 0.f;
+  float ev;
+  const float mw = softmax_wave_terms(u, valid, ev);
   double r[6] = {(double)ev, (double)ev * ev, sf[0], sf[1], sf[2], sf[3]};
-  wave_sum_dpp_n(r);
-  if ((threadIdx.x & 63) == 0) {
-    shf[w] = mw;
-    shd[2 * w] = r[0];
-    shd[2 * w + 1] = r[1];
+  wave_sum_dpp_n(r);  // the softmax sums and the four slot t-1 sums in one fused reduction
+  softmax_wave_put(mw, r[0], r[1], shf, shd);
+  if ((threadIdx.x & 63) == 0)
 #pragma unroll
     for (int k = 0; k < 4; ++k) shd[32 + 4 * w + k] = r[2 + k];
-  }
 }
 // after the barrier
 __device__ __forceinline__ void merge_partials_quad(double *sm, double *fin, const float *shf, const double *shd) {
   if (threadIdx.x == 0) {
     float m = shf[0];
     for (int k = 1; k < 16; ++k) m = fmaxf(m, shf[k]);
-    double sum = 0.0, sq = 0.0;
-    for (int k = 0; k < 16; ++k)
-      if (shf[k] > -INFINITY) {
-        const double f = (double)expf(shf[k] - m);
-        sum += shd[2 * k] * f;
-        sq += shd[2 * k + 1] * f * f;
-      }
-    sm[0] = m;
-    sm[1] = sum;
-    sm[2] = sq;
+    softmax_merge_waves(16, m, m, shf, shd, sm);
     sm[3] = 0.0;
   } else if (fin && threadIdx.x >= 64 && threadIdx.x < 68) {  // encoder t-waves 8, 10, 12, 14 in order
     const int k = threadIdx.x - 64;
@@ -1376,7 +1331,6 @@ __device__ __forceinline__ void merge_partials_quad(double *sm, double *fin, con
 // runs BESIDE the nf_dyn forward: the launch costs proposal + max(nf_dyn forward, encoder)
 // instead of their sum, at four waves per SIMD.  While it waits for the proposal the encoder
 // t-wave normalises slot t-1's particles (the deferred normalisation).  1024 threads per tile.
-template <bool MERGED>
 __device__ __forceinline__ void quad_part(const nfdpf_filter_desc &d, const TiledWs &ws) {
   __shared__ StepShared L;
   __shared__ __attribute__((aligned(8))) float xbuf[8 * kTile];              // flow-pair hand-offs (pair_swap)
@@ -1401,8 +1355,8 @@ __device__ __forceinline__ void quad_part(const nfdpf_filter_desc &d, const Tile
   const bool valid = i < d.N;
   PropIn in{};
   float lr = 0.f;
-  // with the merged front + dyn launch, slot t-1's deferred normalisation runs here (encoder t-wave)
-  const bool defer_here = MERGED && d.defer_norm && d.t > 0 && enc && role == 0;
+  // the merged front + dyn launch leaves slot t-1's deferred normalisation to this one (encoder t-wave)
+  const bool defer_here = d.defer_norm && d.t > 0 && enc && role == 0;
   PrevIn pv{};
   EncFrag2 ef{};
   if (enc) ef = enc_frag2_load(d.pe_params);  // the encoder's weight fragments, once
@@ -1421,17 +1375,9 @@ __device__ __forceinline__ void quad_part(const nfdpf_filter_desc &d, const Tile
   if (threadIdx.x < 4) qflag[threadIdx.x] = 0;
   if (threadIdx.x >= 4 && threadIdx.x < 8) rflag[threadIdx.x - 4] = 0;
   const int ncb = d.n_flows * 4 * kH;
-  if (threadIdx.x < ncb)
-    reinterpret_cast<float *>(L.cb_dyn)[split_cb_index(threadIdx.x)] = ws.cb_dyn[b * kCb + threadIdx.x];
-  if (threadIdx.x >= kTile && threadIdx.x - kTile < ncb) {
-    // finish the proposal fold: the encoding columns came from K1, add [mean, std] of x_dyn
-    const int k = threadIdx.x - kTile;
-    const Ctx4 cp = tiled_ctx(ws.st_dyn, b, tiles, d.N);
-    const float c4[4] = {cp.m0, cp.m1, cp.s0, cp.s1};
-    const FoldRef r = fold_ref(d.cond_params, net_size<1, kH>(d.E + 4), k);
-    reinterpret_cast<float *>(L.cb_cond)[split_cb_index(k)] =
-        fold_acc(r, d.E + 4, ws.cb_cond[b * kCb + k], c4, d.E, d.E + 4);
-  }
+  if (threadIdx.x < ncb) cb_dyn_to_lds<true>(ws, L, b, threadIdx.x);
+  if (threadIdx.x >= kTile && threadIdx.x - kTile < ncb)
+    prop_fold_to_lds<true>(d, ws, L, b, tiles, (int)(threadIdx.x - kTile), ws.st_dyn);
   __syncthreads();
   double sf[4] = {0, 0, 0, 0};
   float u = 0.f;
@@ -1480,10 +1426,7 @@ __device__ __forceinline__ void quad_part(const nfdpf_filter_desc &d, const Tile
       const float p = prev_p_of(pv, rn_prev, shifted, lw, lk);
       if (shifted) Sp.hlik[i] = lk;
       Sp.hp[i] = p;
-      sf[0] = (double)p * p;
-      sf[1] = (double)p * pv.x0;
-      sf[2] = (double)p * pv.x1;
-      sf[3] = lw;
+      fin_terms(p, pv.x0, pv.x1, lw, sf);
     }
     // valid lanes are a prefix of the wave: it has work iff its first lane has
     if (tile * kTile + g * 64 < d.N) {
@@ -1510,13 +1453,12 @@ __device__ __forceinline__ void quad_part(const nfdpf_filter_desc &d, const Tile
   wave_partials_quad(u, valid_e, enc, sf, smf, smd);
   __syncthreads();
   double *sm = reinterpret_cast<double *>(d.ess_out) + ((int64_t)b * tiles + tile) * kSm;
-  const bool fin = MERGED && d.defer_norm && d.t > 0;
+  const bool fin = d.defer_norm && d.t > 0;
   merge_partials_quad(sm, fin ? ws.fin + (((int64_t)b * d.T + d.t - 1) * tiles + tile) * 4 : nullptr, smf, smd);
 }
 
-template <bool MERGED>
 __global__ __launch_bounds__(4 * kTile) void tiled_prop_quad_kernel(const nfdpf_filter_desc d, TiledWs ws) {
-  quad_part<MERGED>(d, ws);
+  quad_part(d, ws);
 }
 
 // ---- K3b (phase 2 of an EXTERNAL measurement): raw likelihood from lik_ext
@@ -1565,7 +1507,7 @@ __global__ __launch_bounds__(kTile) void tiled_norm_kernel(const nfdpf_filter_de
     sw = lw;
   }
   double *fin = ws.fin + (((int64_t)b * d.T + d.t) * tiles + tile) * 4;
-  store_sums4(fin, sp2, px, py, sw, shd);
+  block_sum4_store(sp2, px, py, sw, shd, fin);
 }
 
 // per-row prediction / obs-likelihood sums of every step (after the last step)
@@ -1784,14 +1726,15 @@ template <bool NFD, bool NFC, int MEAS>
 static void launch_prop(const nfdpf_filter_desc &d, TiledWs ws, dim3 g, hipStream_t st, hipEvent_t *ev) {
   // the two-role kernel needs a flow chain to overlap with the measurement
   // (a third role splitting the cosine encoder's output layer was measured slower: 16.7 vs
-  // 11.4 us for the compute phase at C2 -- the extra waves duplicate the encoder's first layers)
+  // 11.4 us for the compute phase at C2 -- the extra waves duplicate the encoder's first layers.
+  // Retired; 1ef51b3 is the last commit that holds it.)
   if constexpr (NFD && NFC && MEAS == NFDPF_MEAS_COS) {
     // (merged: the quad launch, flow pair beside encoder pair)
-    if (use_merged(d)) return launch(tiled_prop_quad_kernel<true>, g, 4 * kTile, 0, st, ev, d, ws);
+    if (use_merged(d)) return launch(tiled_prop_quad_kernel, g, 4 * kTile, 0, st, ev, d, ws);
     if (use_split(d)) return launch(tiled_prop_split_kernel, g, 2 * kTile, 0, st, ev, d, ws);
   }
   if constexpr (NFC && MEAS != NFDPF_MEAS_EXTERNAL) {
-    launch(tiled_prop2_kernel<NFD, NFC, MEAS, 2>, g, 2 * kTile, 0, st, ev, d, ws);
+    launch(tiled_prop2_kernel<NFD, NFC, MEAS>, g, 2 * kTile, 0, st, ev, d, ws);
   } else {
     if constexpr (MEAS == NFDPF_MEAS_CRNVP) {  // (NFC is false here: tiled_prop2 takes the conditional proposal)
       if (d.meas_mfma)
@@ -2085,10 +2028,8 @@ extern "C" int nfdpf_filter_step_tiled(const nfdpf_filter_desc *dp, void *worksp
     if (d.phase == 1) return launch_status("nfdpf_filter_step_tiled");
   }
   if (d.measurement == NFDPF_MEAS_EXTERNAL) tiled_extlik_kernel<<<g, kTile, 0, st>>>(d, ws);
-  const bool shift = d.measurement == NFDPF_MEAS_CRNVP || d.measurement == NFDPF_MEAS_GAUSSIAN ||
-                     d.measurement == NFDPF_MEAS_EXTERNAL;
   if (!d.defer_norm || d.t == d.T - 1) {  // deferred: the next step's launches normalise slot t
-    if (shift)
+    if (shifted_meas(d.measurement))
       tiled_norm_kernel<true><<<g, kTile, 0, st>>>(d, ws);
     else
       tiled_norm_kernel<false><<<g, kTile, 0, st>>>(d, ws);

@@ -639,6 +639,37 @@ def test_split_nets_match_pair_layout(gated):
     assert torch.allclose(a.pred[:, :2], b.pred[:, :2], rtol=1e-4, atol=1e-2)
 
 
+@pytest.mark.parametrize("gated", [True, False])
+def test_split_prop_long_rows(gated):
+    """The wave-pair layout on rows too long for the merged front launch (N > 4096: use_merged
+    is false, use_split and use_rows hold), against the one-wave pair layout.  With split_nets
+    each step launches tiled_rows_kernel, tiled_front_kernel<true>, tiled_dyn_kernel<true> and
+    tiled_prop_split_kernel -- the only shape that reaches the last one (rows up to 4096 take the
+    quad launch).  N = 4100: 17 tiles, the last with 4 valid lanes, so the softmax partials of
+    waves without a valid lane are merged too."""
+    from nfdpf.engine import FilterConfig, FilterEngine
+    fx = load("e2e_c2.npz")
+    models = _Models(weights(fx), e2e_cfg(fx))
+    B, N, T = 2, 4100, 3
+    g = torch.Generator().manual_seed(18)
+    enc = torch.randn(B, T, 32, generator=g).to(DEV)
+    start = (torch.randn(B, 4, generator=g) * 10).to(DEV)
+    vel = (torch.randn(B, T, 2, generator=g) * 3).to(DEV)
+    out = {}
+    for split in (False, True):
+        cfg = FilterConfig(N=N, NF_dyn=True, NF_cond=True, measurement="cos", resampler="soft",
+                           force_resample=not gated, seed=31, kernel="tiled", split_nets=split)
+        out[split] = FilterEngine(cfg, models).run(enc, start, vel)
+    a, b = out[False], out[True]
+    assert torch.equal(a.noise, b.noise)
+    agree = (a.index == b.index).float().mean().item()
+    assert agree > (0.999 if gated else 0.99), agree  # see test_tiled_matches_fused
+    assert torch.allclose(a.particles[:, :2], b.particles[:, :2], rtol=1e-4, atol=1e-2)
+    assert torch.allclose(a.jac[:, :2], b.jac[:, :2], rtol=1e-4, atol=1e-4)
+    assert torch.allclose(a.prior[:, :2], b.prior[:, :2], rtol=1e-4, atol=1e-3)
+    assert torch.allclose(a.pred[:, :2], b.pred[:, :2], rtol=1e-4, atol=1e-2)
+
+
 @pytest.mark.parametrize("aligned", [False, True])
 def test_speculative_gate_matches_exchange(aligned, monkeypatch):
     """Speculative-gate mode (every gate assumed off, verified after the pass from all steps'
