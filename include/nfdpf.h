@@ -311,7 +311,29 @@ NFDPF_API int nfdpf_cglow_measurement(const float *pe_params, const float *glow_
 NFDPF_API int nfdpf_cglow_flow(const float *glow_params, int K, const float *x, const float *y, int64_t M,
                                float *z, float *nll, void *stream);
 
-/* Backward of the two CGLOW entry points above (training; the autograd
+/* The two entry points above for the configurations they do not take: num_levels L in 1..2
+ * (the reference's -L flag) and / or a learnt top prior (--learn_top), flow_depth K in 1..4;
+ * forward only, one launch per call, no workspace (csrc/cglow_levels.hip).  At L = 2 the K
+ * level-1 steps are followed by Split2d(12) -- the Gaussian term of z2 under the prior
+ * tanh(conv(z1)) joins the log-det, z1 goes on --, a squeeze to 24 x 2 x 2 and K level-2 steps.
+ *   glow_params: K steps of 7980 floats as nfdpf_cglow_measurement; at L = 2 then the Split2d
+ *     conv (tap-major [3][3][6][12], 12 biases: 660 floats) and K level-2 steps of 21168 floats
+ *     (csrc/cglow_levels.hpp; packed by nfdpf.pack.cglow_levels_tensors).
+ *   top: [new_mean | new_logs] of the top Gaussian, 96 floats each at L = 2 ([24,2,2]), 192
+ *     each at L = 1 ([12,4,4]); NULL = zeros (learn_top off).  nfdpf.pack puts it at the
+ *     blob's tail: nfdpf_cglow_levels_params_size(K, L, learn_top) counts it when learn_top
+ *     != 0, and returns -1 for K outside 1..4 or L outside 1..2.
+ *   nfdpf_cglow_levels_flow: z (NULL: not written) is the FINAL z only, 96 floats per sample
+ *     at L = 2 and 192 at L = 1; dimensions stays 192 in nll.
+ * K or L outside their ranges: NFDPF_EINVAL, nothing launched. */
+NFDPF_API int64_t nfdpf_cglow_levels_params_size(int K, int L, int learn_top);
+NFDPF_API int nfdpf_cglow_levels_measurement(const float *pe_params, const float *glow_params, int K, int L,
+                                             const float *top, const float *enc, int64_t enc_rs, const float *x,
+                                             int64_t x_rs, int B, int N, float *lik, int64_t lik_rs, void *stream);
+NFDPF_API int nfdpf_cglow_levels_flow(const float *glow_params, int K, int L, const float *top, const float *x,
+                                      const float *y, int64_t M, float *z, float *nll, void *stream);
+
+/* Backward of the two CGLOW entry points nfdpf_cglow_measurement / nfdpf_cglow_flow (training; the autograd
  * gradient of nf/cglow/modules.py + CGlowModel.py:167-176, d log|det W| / dW = W^-T).
  * Deterministic (fixed-order per-workgroup partials in the workspace, reduced in order).
  * K in 1..4 as the forward entry points; K > 1 runs one launch per step from the last step to

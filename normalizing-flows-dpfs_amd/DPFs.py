@@ -26,7 +26,7 @@ from model.models import (build_conditional_glow, build_conditional_nf, build_de
                           measurement_model_cglow, measurement_model_cnf, measurement_model_cosine_distance,
                           measurement_model_Gaussian, measurement_model_NN, motion_update, nf_dynamic_model,
                           proposal_likelihood)
-from nfdpf._lib import meas_width_supported, require_meas_width
+from nfdpf._lib import NfdpfError, meas_width_supported, require_meas_width
 from nfdpf.engine import FilterConfig, FilterEngine, ShardInfo
 from nfdpf.gradsync import GradBucket, global_mean, sharded_supervised_loss, world_size
 from resamplers.resamplers import resampler
@@ -61,6 +61,10 @@ class DPF(nn.Module):
         if args.measurement in ("cos", "CRNVP", "NN", "gaussian"):
             # (the HIP measurement kernels are built per width: refuse here, not inside the first step)
             require_meas_width(args.measurement, args.hiddensize, "DPF")
+        if args.measurement == "CGLOW" and getattr(args, "num_levels", 1) > 2:
+            # (the CGLOW kernels take one or two levels: refuse here, not inside the first step)
+            raise NfdpfError(f"DPF: the CGLOW measurement's HIP kernels are built for num_levels L in 1..2 "
+                             f"(got -L {args.num_levels})")
         self.state_dim = 2  # particles are 2-D positions (DPFs.py:31)
         self.lr = args.lr
         self.alpha = args.alpha
@@ -176,7 +180,8 @@ class DPF(nn.Module):
 
     def _fused_supported(self):
         if self.measurement == "CGLOW":
-            return self.hidden_size == 192 and 1 <= getattr(self.param, "flow_depth", 1) <= 4
+            return (self.hidden_size == 192 and 1 <= getattr(self.param, "flow_depth", 1) <= 4
+                    and 1 <= getattr(self.param, "num_levels", 1) <= 2)
         return self.measurement in ("cos", "CRNVP", "NN", "gaussian") and \
             meas_width_supported(self.measurement, self.hidden_size)
 

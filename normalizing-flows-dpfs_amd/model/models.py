@@ -391,6 +391,24 @@ class _CglowRunner:
         return (g_enc.to(enc.dtype), gx.to(x.dtype)), res
 
 
+class _CglowLevelsRunner(_CglowRunner):
+    """_CglowRunner for the configurations its kernel does not take (L = 2 and / or learn_top):
+    the levels kernel forward (csrc/cglow_levels.hip); no HIP backward -- the bounded PyTorch
+    recompute differentiates torch_forward_raw."""
+
+    def hip(self, enc, x):
+        from nfdpf.pack import cglow_levels_tensors
+        m = self.model
+        g = m.CGLOW
+        pe = blob(m, "pe", m.particle_encoder, lambda: encoder_tensors(m.particle_encoder), x.device)
+        glow = blob(m, "glow_levels", g, lambda: cglow_levels_tensors(g), x.device)
+        return (_ops.cglow_levels_measurement(pe, glow, enc.float(), x.float(), K=g.flow.K, L=g.flow.L,
+                                              learn_top=g.learn_top),)
+
+    def hip_backward(self, enc, x, gouts):
+        return None
+
+
 class measurement_model_cglow(nn.Module):
     """Conditional-GLOW likelihood (model/models.py:280-303)."""
 
@@ -404,10 +422,15 @@ class measurement_model_cglow(nn.Module):
         with its 12x12 log-determinant, affine coupling, Gaussian log-prob), then the row-max
         shift.  Under autograd the particle encoder and every CGLOW parameter get their
         gradients through the recompute backward of _CglowRunner."""
-        if not self.CGLOW.kernel_supported():
-            raise NfdpfError("measurement_model_cglow: the HIP kernel is built for the reference's default CGLOW "
-                             "with flow_depth K in 1..4 (L = 1, 3x8x8, learn_top off, 256 bins)")
-        lik = _ag.apply(_CglowRunner(self), (encodings, update_particles), list(self.parameters()))[0]
+        if self.CGLOW.kernel_supported():
+            runner = _CglowRunner(self)
+        elif self.CGLOW.levels_kernel_supported():
+            # L = 2 and / or learn_top: csrc/cglow_levels.hip, gradients through the bounded recompute
+            runner = _CglowLevelsRunner(self)
+        else:
+            raise NfdpfError("measurement_model_cglow: the HIP kernels are built for the reference's default CGLOW "
+                             "with flow_depth K in 1..4 and num_levels L in 1..2 (3x8x8, hidden 8 / 16 / 8, 256 bins)")
+        lik = _ag.apply(runner, (encodings, update_particles), list(self.parameters()))[0]
         return lik - lik.max(dim=-1, keepdim=True)[0]
 
     def torch_forward_raw(self, encodings, particles):

@@ -5,10 +5,12 @@ keys (flow.layers.{k}...., new_mean, new_logs), same forward / reverse API.
 -> K x [cond-actnorm, cond-1x1 conv with a per-sample 12x12 slogdet, cond-affine coupling] ->
 Gaussian log-prob, CGlowModel.py:167-176) -- runs as one HIP kernel (csrc/cglow.hip,
 nfdpf_cglow_flow) for the configuration the reference's flags give (K in 1..4, L = 1, x_size =
-y_size = (3, 8, 8), learn_top off) and returns the reference's (z, nll).  Under autograd its
-backward differentiates ``torch_forward``, a PyTorch restatement of the same math run on the
-saved inputs (nfdpf.autograd; the forward value is the kernel's).  ``reverse=True`` (sampling;
-the DPF never calls it) runs the layers' PyTorch reverse."""
+y_size = (3, 8, 8), learn_top off) and returns the reference's (z, nll); with L = 2 (Split2d and
+a second level on 24 x 2 x 2) and / or learn_top it runs as one launch of csrc/cglow_levels.hip
+(nfdpf_cglow_levels_flow).  Under autograd the backward is the HIP one (csrc/cglow_bwd.hip) at
+L = 1 without learn_top; otherwise it differentiates ``torch_forward``, a PyTorch restatement of
+the same math run on the saved inputs (nfdpf.autograd; the forward value is the kernel's).
+``reverse=True`` (sampling; the DPF never calls it) runs the layers' PyTorch reverse."""
 import numpy as np
 import torch
 import torch.nn as nn
@@ -75,6 +77,13 @@ class CondGlow(nn.Module):
         return y, logdet
 
 
+def _hidden_sizes(flow):
+    """(x_hidden_channels, x_hidden_size, y_hidden_channels) of a CondGlow's first step."""
+    st = next(l for l in flow.layers if isinstance(l, CondGlowStep))
+    lin = [m for m in st.actnorm.x_Linear if isinstance(m, nn.Linear)]
+    return lin[0].in_features, lin[0].out_features, st.affine.f[0].out_channels
+
+
 class _FlowRunner:
     """nfdpf.autograd runner: the HIP kernel forward, the PyTorch restatement for backward."""
 
@@ -103,6 +112,22 @@ class _FlowRunner:
         return (gx, gy), res
 
 
+class _LevelsFlowRunner(_FlowRunner):
+    """The runner of the configurations _FlowRunner's kernel does not take (L = 2 and / or
+    learn_top): the levels kernel forward (csrc/cglow_levels.hip); no HIP backward -- the
+    recompute path differentiates torch_forward, which is general in L and learn_top."""
+
+    def hip(self, x, y):
+        from nfdpf import ops
+        from nfdpf.pack import blob, cglow_levels_tensors
+        m = self.model
+        glow = blob(m, "glow_levels", m, lambda: cglow_levels_tensors(m), x.device)
+        return ops.cglow_levels_flow(glow, x, y, K=m.flow.K, L=m.flow.L, learn_top=m.learn_top)
+
+    def hip_backward(self, x, y, gouts):
+        return None
+
+
 class CondGlowModel(nn.Module):
     def __init__(self, args):
         super().__init__()
@@ -129,9 +154,19 @@ class CondGlowModel(nn.Module):
         return (1 <= f.K <= 4 and f.L == 1 and not self.learn_top and float(self.n_bins) == 256.0
                 and list(f.output_shapes[-1][1:]) == [12, 4, 4])
 
+    def levels_kernel_supported(self) -> bool:
+        """The configurations csrc/cglow_levels.hip is built for: K in 1..4, L in 1..2, any
+        learn_top, 256 bins, 3x8x8 x and y, hidden 8 / 16 / 8."""
+        f = self.flow
+        return (1 <= f.K <= 4 and 1 <= f.L <= 2 and float(self.n_bins) == 256.0
+                and list(f.output_shapes[-1][1:]) == ([12, 4, 4] if f.L == 1 else [24, 2, 2])
+                and _hidden_sizes(f) == (8, 16, 8))
+
     def forward(self, x=0.0, y=None, eps_std=1.0, reverse=False):
         """reverse=False: (z, nll) of y given the condition x (CGlowModel.py:167-176), on the
-        HIP kernel.  reverse=True: a sample (or the inverse of a given y) and its log-det
+        HIP kernel: csrc/cglow.hip at L = 1 without learn_top, csrc/cglow_levels.hip at L = 2
+        and / or with learn_top (z is the final z, [M, 24, 2, 2] at L = 2).
+        reverse=True: a sample (or the inverse of a given y) and its log-det
         (:178-184), PyTorch (off the DPF path)."""
         if reverse:
             with torch.no_grad():
@@ -139,11 +174,14 @@ class CondGlowModel(nn.Module):
                 if y is None:
                     y = modules.GaussianDiag.batchsample(x.size(0), mean, logs, eps_std)
                 return self.flow(x, y, eps_std=eps_std, reverse=True)
-        if not self.kernel_supported():
-            raise NfdpfError("CondGlowModel.forward: the HIP kernel is built for K in 1..4, L = 1, 3x8x8 inputs, "
-                             "learn_top off and 256 bins (the reference's defaults)")
-        z, nll = _ag.apply(_FlowRunner(self), (x.float().contiguous(), y.float().contiguous()),
-                           list(self.parameters()))
+        if self.kernel_supported():
+            runner = _FlowRunner(self)
+        elif self.levels_kernel_supported():
+            runner = _LevelsFlowRunner(self)
+        else:
+            raise NfdpfError("CondGlowModel.forward: the HIP kernels are built for K in 1..4, L in 1..2, 3x8x8 "
+                             "inputs, hidden sizes 8 / 16 / 8 and 256 bins")
+        z, nll = _ag.apply(runner, (x.float().contiguous(), y.float().contiguous()), list(self.parameters()))
         return z, nll
 
     def torch_forward(self, x, y):

@@ -2,8 +2,8 @@
 structure and initialisation of each layer, so checkpoints keep their state_dict keys, and
 each layer's forward / reverse in PyTorch.
 
-The likelihood evaluation the DPF runs (CondGlowModel.forward, K in 1..4, L = 1) is ONE HIP kernel
-(csrc/cglow.hip).  The PyTorch forwards below are not on that path: they are what autograd
+The likelihood evaluation the DPF runs (CondGlowModel.forward, K in 1..4, L in 1..2) is ONE HIP
+kernel launch (csrc/cglow.hip; csrc/cglow_levels.hip at L = 2 or with learn_top).  The PyTorch forwards below are not on that path: they are what autograd
 differentiates when CGLOW is trained (nfdpf.autograd re-runs them on the saved inputs, the
 forward value still being the kernel's) and the reverse (sampling) direction, which the DPF
 never calls."""

@@ -120,6 +120,11 @@ SIGNATURES = {
     "nfdpf_cglow_measurement": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_int64, c_int,
                                         c_int, c_void_p, c_int64, c_void_p]),
     "nfdpf_cglow_flow": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "nfdpf_cglow_levels_params_size": (c_int64, [c_int, c_int, c_int]),
+    "nfdpf_cglow_levels_measurement": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int64,
+                                               c_void_p, c_int64, c_int, c_int, c_void_p, c_int64, c_void_p]),
+    "nfdpf_cglow_levels_flow": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
+                                        c_void_p, c_void_p]),
     "nfdpf_cglow_backward_workspace": (c_int64, [c_int64]),
     "nfdpf_cglow_backward_workspace_k": (c_int64, [c_int64, c_int]),
     "nfdpf_cglow_measurement_backward": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_int64,

@@ -32,7 +32,7 @@ import torch.distributed as dist
 
 from . import _lib as L
 from . import ops
-from .pack import (blob, cglow_tensors, encoder_tensors, filter_flow_tensors, flows_tensors,
+from .pack import (blob, cglow_levels_tensors, cglow_tensors, encoder_tensors, filter_flow_tensors, flows_tensors,
                    paired_mlp_tensors, pass_flow_tensors, splittable)
 
 
@@ -491,7 +491,11 @@ class FilterEngine:
         elif c.measurement == "NN":
             meas = blob(m, "meas", m.likelihood_est, lambda: paired_mlp_tensors(m.likelihood_est), dev)
         elif c.measurement == "CGLOW":
-            meas = blob(m, "glow", m.cglow_measurement, lambda: cglow_tensors(m.cglow_measurement), dev)
+            g = m.cglow_measurement
+            if g.kernel_supported():
+                meas = blob(m, "glow", g, lambda: cglow_tensors(g), dev)
+            else:  # L = 2 and / or learn_top: the levels kernel's layout (csrc/cglow_levels.hpp)
+                meas = blob(m, "glow_levels", g, lambda: cglow_levels_tensors(g), dev)
         return dyn, cond, pe, meas
 
     # -- main loop --------------------------------------------------------------------------
@@ -534,6 +538,7 @@ class FilterEngine:
         if wide:
             L.require_meas_width(c.measurement, E, "FilterEngine.run")
         external = self._external = c.measurement == "CGLOW" or wide
+        glow_levels = c.measurement == "CGLOW" and not self.m.cglow_measurement.kernel_supported()
         N = c.N
         shard = shard or ShardInfo(1, 0, B, 0, None)
         if shard.world == 1 and shard.B_global != B:
@@ -862,6 +867,10 @@ class FilterEngine:
                 if wide:
                     ops.measurement(c.measurement, pe, meas, c.n_flows, enc[:, t], hx[:, t], c.meas_prior_std,
                                     out=lik_ext)
+                elif glow_levels:  # L = 2 and / or learn_top (the blob of _blobs is in its layout)
+                    g = self.m.cglow_measurement
+                    ops.cglow_levels_measurement(pe, meas, enc[:, t], hx[:, t], K=g.flow.K, L=g.flow.L,
+                                                 learn_top=g.learn_top, out=lik_ext)
                 else:
                     ops.cglow_measurement(pe, meas, enc[:, t], hx[:, t], K=self.m.cglow_measurement.flow.K,
                                           out=lik_ext)

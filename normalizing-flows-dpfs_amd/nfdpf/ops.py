@@ -12,7 +12,7 @@ from typing import Optional
 import torch
 
 from . import _lib as L
-from ._lib import check, lib, ptr, require_device, stream_ptr
+from ._lib import NfdpfError, check, lib, ptr, require_device, stream_ptr
 
 f32 = torch.float32
 
@@ -515,6 +515,57 @@ def cglow_flow(glow_blob, x, y, K=1):
     nll = torch.empty((M,), device=x.device, dtype=f32)
     check(lib().nfdpf_cglow_flow(ptr(_c(glow_blob)), int(K), ptr(x), ptr(y), int(M), ptr(z), ptr(nll),
                                  stream_ptr(x.device)), "nfdpf_cglow_flow")
+    return z, nll
+
+
+def _levels_blob(glow_blob, K, L, learn_top, what):
+    """Check a cglow_levels_tensors blob against (K, L, learn_top); -> (blob, pointer to its
+    [new_mean | new_logs] tail or None)."""
+    n = int(lib().nfdpf_cglow_levels_params_size(int(K), int(L), int(bool(learn_top))))
+    if n < 0:
+        raise NfdpfError(f"{what}: built for flow_depth K in 1..4 and num_levels L in 1..2 (got K = {K}, L = {L})")
+    if int(glow_blob.numel()) != n:
+        raise NfdpfError(f"{what}: parameter blob does not match K = {K}, L = {L}, learn_top = {bool(learn_top)} "
+                            f"({int(glow_blob.numel())} floats, expected {n})")
+    glow_blob = _c(glow_blob)
+    nz = 96 if int(L) == 2 else 192
+    return glow_blob, (ptr(glow_blob[n - 2 * nz:]) if learn_top else None)
+
+
+def cglow_levels_measurement(pe_blob, glow_blob, enc, x, K=1, L=1, learn_top=False, out=None):
+    """cglow_measurement for num_levels L in 1..2 and / or a learnt top prior
+    (nfdpf_cglow_levels_measurement; glow_blob from nfdpf.pack.cglow_levels_tensors): enc [B, 192]
+    (rows may be strided), x [B, N, 2] -> raw lik [B, N], no row-max shift."""
+    require_device(x, "cglow_levels_measurement")
+    B, N, _ = x.shape
+    if x.stride(2) != 1 or x.stride(1) != 2:
+        x = x.contiguous()
+    if enc.stride(-1) != 1:
+        enc = enc.contiguous()
+    if enc.shape[-1] != 192:
+        raise NfdpfError("cglow_levels_measurement: frame encodings must be 192 wide (--hiddensize 192)")
+    glow_blob, top = _levels_blob(glow_blob, K, L, learn_top, "cglow_levels_measurement")
+    lik = out if out is not None else torch.empty((B, N), device=x.device, dtype=f32)
+    check(lib().nfdpf_cglow_levels_measurement(ptr(pe_blob), ptr(glow_blob), int(K), int(L), top, ptr(enc),
+                                               enc.stride(0), ptr(x), x.stride(0), B, N, ptr(lik), lik.stride(0),
+                                               stream_ptr(x.device)), "nfdpf_cglow_levels_measurement")
+    return lik
+
+
+def cglow_levels_flow(glow_blob, x, y, K=1, L=1, learn_top=False):
+    """cglow_flow for num_levels L in 1..2 and / or a learnt top prior (nfdpf_cglow_levels_flow):
+    x, y [M,3,8,8] -> (the final z, [M,24,2,2] at L = 2 and [M,12,4,4] at L = 1; nll [M])."""
+    require_device(x, "cglow_levels_flow")
+    M = x.shape[0]
+    if tuple(x.shape[1:]) != (3, 8, 8) or tuple(y.shape) != tuple(x.shape):
+        raise NfdpfError(f"cglow_levels_flow: x and y must both be [M, 3, 8, 8] (got {tuple(x.shape)}, "
+                            f"{tuple(y.shape)})")
+    x, y = _c(x), _c(y)
+    glow_blob, top = _levels_blob(glow_blob, K, L, learn_top, "cglow_levels_flow")
+    z = torch.empty((M, 24, 2, 2) if int(L) == 2 else (M, 12, 4, 4), device=x.device, dtype=f32)
+    nll = torch.empty((M,), device=x.device, dtype=f32)
+    check(lib().nfdpf_cglow_levels_flow(ptr(glow_blob), int(K), int(L), top, ptr(x), ptr(y), int(M), ptr(z), ptr(nll),
+                                        stream_ptr(x.device)), "nfdpf_cglow_levels_flow")
     return z, nll
 
 

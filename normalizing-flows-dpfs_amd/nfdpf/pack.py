@@ -117,6 +117,22 @@ def _cond_net_tensors(m: nn.Module, get=_same):
 CGLOW_MAX_K = 4  # flow depths the CGLOW kernels take (csrc/cglow.hpp kMaxK)
 
 
+def _cglow_step_tensors(st: nn.Module, get=_same):
+    """One CondGlowStep: the actnorm net, the 1x1-conv net, then the affine coupling
+    (modules.py:258-303) in the kernel layout (csrc/cglow.hpp Aff, csrc/cglow_levels.hpp AffL):
+    resize_x / f convolutions tap-major, output channel fastest."""
+    a = st.affine
+    r0, r2, r4 = [l for l in a.resize_x if isinstance(l, nn.Conv2d)]
+    f0, f2, f4 = [l for l in a.f if isinstance(l, nn.Conv2d)]
+    w2 = get(f2.weight)
+    return (_cond_net_tensors(st.actnorm, get) + _cond_net_tensors(st.invconv, get) +
+            [_taps_last(get(r0.weight)), get(r0.bias), _taps_last(get(r2.weight)), get(r2.bias),
+             _taps_last(get(r4.weight)), get(r4.bias),
+             _taps_last(get(f0.weight)), get(f0.actnorm.bias), get(f0.actnorm.logs),
+             w2.reshape(w2.shape[0], -1).t(), get(f2.actnorm.bias), get(f2.actnorm.logs),
+             _taps_last(get(f4.weight)), get(f4.bias), get(f4.logs), get(f4.newbias)])
+
+
 def cglow_tensors(glow: nn.Module, get=_same):
     """CondGlowModel (nf/cglow/CGlowModel.py) with K in 1..4, L = 1: per CondGlowStep, in model
     order (step k at k * kStep floats), the actnorm net, 1x1-conv net, then the affine coupling
@@ -127,16 +143,31 @@ def cglow_tensors(glow: nn.Module, get=_same):
         raise ValueError(f"the CGLOW kernel is built for flow_depth K in 1..{CGLOW_MAX_K} (got {len(steps)} steps)")
     out = []
     for st in steps:
-        a = st.affine
-        r0, r2, r4 = [l for l in a.resize_x if isinstance(l, nn.Conv2d)]
-        f0, f2, f4 = [l for l in a.f if isinstance(l, nn.Conv2d)]
-        w2 = get(f2.weight)
-        out += (_cond_net_tensors(st.actnorm, get) + _cond_net_tensors(st.invconv, get) +
-                [_taps_last(get(r0.weight)), get(r0.bias), _taps_last(get(r2.weight)), get(r2.bias),
-                 _taps_last(get(r4.weight)), get(r4.bias),
-                 _taps_last(get(f0.weight)), get(f0.actnorm.bias), get(f0.actnorm.logs),
-                 w2.reshape(w2.shape[0], -1).t(), get(f2.actnorm.bias), get(f2.actnorm.logs),
-                 _taps_last(get(f4.weight)), get(f4.bias), get(f4.logs), get(f4.newbias)])
+        out += _cglow_step_tensors(st, get)
+    return out
+
+
+CGLOW_MAX_L = 2  # levels the levels kernel takes (csrc/cglow_levels.hpp kMaxL)
+
+
+def cglow_levels_tensors(glow: nn.Module, get=_same):
+    """CondGlowModel with K in 1..4, L in 1..2 and any learn_top, for csrc/cglow_levels.hip
+    (layout: csrc/cglow_levels.hpp): the K level-1 steps as cglow_tensors; at L = 2 the Split2d
+    conv tap-major and its bias, then the K level-2 steps, each as _cglow_step_tensors; with
+    learn_top the tail [new_mean | new_logs].  A pure gather, like cglow_tensors."""
+    K, L = glow.flow.K, glow.flow.L
+    if not (1 <= K <= CGLOW_MAX_K and 1 <= L <= CGLOW_MAX_L):
+        raise ValueError(f"the CGLOW levels kernel is built for flow_depth K in 1..{CGLOW_MAX_K} and num_levels L in "
+                         f"1..{CGLOW_MAX_L} (got K = {K}, L = {L})")
+    out = []
+    for layer in glow.flow.layers:
+        if hasattr(layer, "affine"):
+            out += _cglow_step_tensors(layer, get)
+        elif hasattr(layer, "conv"):  # Split2d
+            conv = layer.conv[0]
+            out += [_taps_last(get(conv.weight)), get(conv.bias)]
+    if glow.learn_top:
+        out += [get(glow.new_mean), get(glow.new_logs)]
     return out
 
 
