@@ -358,6 +358,39 @@ NFDPF_API int nfdpf_cglow_flow_backward(const float *glow_params, int K, const f
                                         const float *g_z, const float *g_nll, float *g_x, float *g_y,
                                         float *g_glow, void *workspace, void *stream);
 
+/* Backward of nfdpf_cglow_levels_measurement / nfdpf_cglow_levels_flow (training;
+ * csrc/cglow_levels_bwd.hip): flow_depth K in 1..4 with L = 1 and a learnt top prior, or with
+ * L = 2 and either learn_top setting ((L = 1, top NULL) is accepted too: the chain of
+ * nfdpf_cglow_measurement_backward with the Gaussian term in its own launch).  K outside 1..4 or
+ * L outside 1..2: NFDPF_EINVAL with a message, nothing launched (the workspace query: -1).
+ * One launch per stage, from the top down: a forward launch leaves every step's output in the
+ * workspace; a small kernel takes the top Gaussian (dL/dz_final = g_z plus the particle's weight
+ * on GaussianDiag.logp, and the gradients of new_mean / new_logs); at L = 2 the K level-2 steps
+ * (24 x 2 x 2, W^-1 of the per-particle 24 x 24 matrix by Gauss-Jordan), then Split2d's Gaussian
+ * term and the un-squeeze; then the K level-1 steps run as the chain of
+ * nfdpf_cglow_measurement_backward without their Gaussian term, step 0 with the particle
+ * encoder's backward.  Every sum over particles has a fixed order (per-workgroup partial rows in
+ * the workspace, summed in row order): deterministic, no atomics.
+ *   arguments as the forward entry points and as nfdpf_cglow_measurement_backward /
+ *   nfdpf_cglow_flow_backward; top: the blob's [new_mean | new_logs] tail, NULL = zeros and no
+ *   gradient for it (learn_top off).
+ *   g_glow: the layout of nfdpf_cglow_levels_params_size(K, L, top != NULL), the gradient of
+ *     [new_mean | new_logs] at its tail when top is given.
+ *   g_z (flow form): dL/d(final z), 96 floats per sample at L = 2, 192 at L = 1; NULL = 0.
+ *   B = 0 or M = 0: the parameter gradients are zeroed, nothing else runs.
+ *   workspace: nfdpf_cglow_levels_backward_workspace(B*N or M, K, L) bytes: the partial rows,
+ *     K + 4 buffers of M * 192 floats and, at L = 2, K + 1 of M * 96 floats. */
+NFDPF_API int64_t nfdpf_cglow_levels_backward_workspace(int64_t M, int K, int L);
+NFDPF_API int nfdpf_cglow_levels_measurement_backward(const float *pe_params, const float *glow_params, int K, int L,
+                                                      const float *top, const float *enc, int64_t enc_rs,
+                                                      const float *x, int64_t x_rs, int B, int N, const float *g_lik,
+                                                      int64_t glik_rs, float *g_x, float *g_y, float *g_glow,
+                                                      float *g_pe, void *workspace, void *stream);
+NFDPF_API int nfdpf_cglow_levels_flow_backward(const float *glow_params, int K, int L, const float *top,
+                                               const float *x, const float *y, int64_t M, const float *g_z,
+                                               const float *g_nll, float *g_x, float *g_y, float *g_glow,
+                                               void *workspace, void *stream);
+
 /* Backward of nfdpf_maf_stack (training): g_out [rows, dim] = dL/d(output), g_logdet [rows]
  * (either may be NULL = 0) -> g_x [rows, dim] = dL/dx and g_params = dL/d(blob), the blob's
  * layout.  dim 2 or 4, hidden 8, n_flows <= 4 (dim 4: <= 2).  workspace: caller-owned,

@@ -42,4 +42,17 @@ constexpr int kMaxK = 4;  // flow depths the kernels take: the blob holds K step
 // cglow.hip, for the K > 1 backward (cglow_bwd.hip): the first `nsteps` steps' outputs
 int cglow_forward_mid(const float *pe, const float *glow, int nsteps, const float *enc, int64_t enc_rs,
                       const float *x, int64_t x_rs, int B, int N, const float *xin, float *zmid, hipStream_t st);
+
+// cglow_bwd.hip, for the chains whose top Gaussian is taken elsewhere (cglow_levels_bwd.hip): the
+// K level-1 steps from K-1 down to 0, every one a !TOP launch of cglow_bwd_kernel.  part: the
+// measurement form (pe, x particles, enc rows, g_up = g_lik) or the flow form (x = the condition
+// [M, 192], enc = y [M, 192], g_up = g_nll), as the arguments of that kernel.  zmid: the steps'
+// outputs z_0 .. z_{K-2} ([M, 192] each, (12, 4, 4)).  gzb / gxb: two [M, 192] hand-over buffers
+// each; on entry gzb[1] holds dL/dz_{K-1} and gxb[1] the condition's gradient so far.  partial:
+// cglow_bwd_partial_floats(M) floats.  g_glow: the K steps' gradients; g_pe may be null.
+int64_t cglow_bwd_partial_floats(int64_t M);
+int cglow_bwd_below(bool part, const float *pe, const float *glow, int K, const float *zmid, const float *enc,
+                    int64_t enc_rs, const float *x, int64_t x_rs, int B, int N, const float *g_up, int64_t gup_rs,
+                    float *const *gzb, float *const *gxb, float *g_y, float *g_x, float *g_glow, float *g_pe,
+                    float *partial, hipStream_t st);
 }  // namespace nfdpf

@@ -1484,7 +1484,43 @@ static int launch_chain(const float *pe, const float *glow, int K, const float *
   return launch_status("cglow_backward");
 }
 
+// The chain with the Gaussian term taken elsewhere (cglow_levels_bwd.hip): every step runs as a
+// !TOP launch, step K-1 reading dL/dz_{K-1} from gzb[1] and the condition's gradient so far
+// from gxb[1]; the hand-over buffers alternate from there as in launch_chain.
+template <bool PART>
+static int launch_below(const float *pe, const float *glow, int K, const float *zmid, const float *enc,
+                        int64_t enc_rs, const float *x, int64_t x_rs, int B, int N, const float *g_up, int64_t gup_rs,
+                        float *const *gzb, float *const *gxb, float *g_y, float *g_x, float *g_glow, float *g_pe,
+                        float *partial, hipStream_t st) {
+  const int64_t M = (int64_t)B * N;
+  const int grid = bwd_grid(M);
+  for (int k = K - 1; k >= 0; --k) {
+    const int cur = (K - 1 - k) & 1;
+    const float *gl = glow + (int64_t)k * kStep;
+    float *gg = g_glow + (int64_t)k * kStep;
+    if (k > 0)
+      launch_step<PART, true, false>(grid, pe, gl, zmid + (int64_t)(k - 1) * M * kE, kE, x, x_rs, B, N, g_up, gup_rs,
+                                     gzb[cur ^ 1], gzb[cur], gxb[cur], gxb[cur ^ 1], gg, nullptr, partial, st);
+    else
+      launch_step<PART, false, false>(grid, pe, gl, enc, enc_rs, x, x_rs, B, N, g_up, gup_rs, gzb[cur ^ 1], g_y, g_x,
+                                      gxb[cur ^ 1], gg, g_pe, partial, st);
+  }
+  return launch_status("cglow_backward");
+}
+
 }  // namespace cgb
+
+int64_t cglow_bwd_partial_floats(int64_t M) { return cgb::partial_floats(M); }
+
+int cglow_bwd_below(bool part, const float *pe, const float *glow, int K, const float *zmid, const float *enc,
+                    int64_t enc_rs, const float *x, int64_t x_rs, int B, int N, const float *g_up, int64_t gup_rs,
+                    float *const *gzb, float *const *gxb, float *g_y, float *g_x, float *g_glow, float *g_pe,
+                    float *partial, hipStream_t st) {
+  return part ? cgb::launch_below<true>(pe, glow, K, zmid, enc, enc_rs, x, x_rs, B, N, g_up, gup_rs, gzb, gxb, g_y,
+                                        g_x, g_glow, g_pe, partial, st)
+              : cgb::launch_below<false>(pe, glow, K, zmid, enc, enc_rs, x, x_rs, B, N, g_up, gup_rs, gzb, gxb, g_y,
+                                         g_x, g_glow, g_pe, partial, st);
+}
 }  // namespace nfdpf
 
 using namespace nfdpf;

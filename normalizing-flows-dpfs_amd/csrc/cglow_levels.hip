@@ -489,10 +489,23 @@ __device__ __noinline__ void split_squeeze(const float *__restrict__ Sp, int tid
   __syncthreads();
 }
 
+// the tile's state S.y (n floats per particle) to buf [M][n] (the MID forward)
+__device__ __forceinline__ void mid_store(float *__restrict__ buf, int n, int64_t g0, int64_t total, int tid) {
+  for (int i = tid; i < kTileP * n; i += kThreads) {
+    const int p = i / n, e = i - p * n;
+    if (g0 + p < total) buf[(g0 + p) * n + e] = S.y[p][e];
+  }
+}
+
 // x: particle (b, i) at x + b * x_rs + 2 i;  enc: row b at enc + b * enc_rs (192 floats);
 // lik: (b, i) at lik + b * lik_rs + i = out_sign * (-nll).  xin non-null: the flow form (the
 // condition given per sample, N = 1, enc = y).  zout (may be null): the final z, nz floats per
 // particle.  top (may be null): [mean | logs] of the top Gaussian, nz floats each.
+// MID (the backward's forward pass, cglow_levels_bwd.hip; L = 2): no likelihood; zout receives
+// every step's output instead -- the K level-1 outputs as [k][M][192] ((12, 4, 4)), then the
+// level-2 inputs / outputs [k][M][96] ((24, 2, 2)), k = 0 the squeezed z1 after Split2d, k = K the
+// final z.
+template <bool MID>
 __global__ __launch_bounds__(kThreads, kWgs) void cglow_levels_kernel(
     const float *__restrict__ pe, const float *__restrict__ glow, const float *__restrict__ top,
     const float *__restrict__ enc, int64_t enc_rs, const float *__restrict__ x, int64_t x_rs, int B, int N,
@@ -560,12 +573,24 @@ __global__ __launch_bounds__(kThreads, kWgs) void cglow_levels_kernel(
     }
     __syncthreads();
 #pragma unroll 1
-    for (int k = 0; k < K; ++k) glow_step<kC, 4>(glow + (int64_t)k * kStep, tid);
+    for (int k = 0; k < K; ++k) {
+      glow_step<kC, 4>(glow + (int64_t)k * kStep, tid);
+      if constexpr (MID) mid_store(zout + (int64_t)k * total * kE, kE, g0, total, tid);
+    }
     if (L == 2) {
       const float *g2 = glow + (int64_t)K * kStep;
       split_squeeze(g2, tid);
+      float *z2mid = MID ? zout + (int64_t)K * total * kE : nullptr;
+      if constexpr (MID) mid_store(z2mid, kC2 * 4, g0, total, tid);
 #pragma unroll 1
-      for (int k = 0; k < K; ++k) glow_step<kC2, 2>(g2 + kSplit + (int64_t)k * Step2::size, tid);
+      for (int k = 0; k < K; ++k) {
+        glow_step<kC2, 2>(g2 + kSplit + (int64_t)k * Step2::size, tid);
+        if constexpr (MID) mid_store(z2mid + (int64_t)(k + 1) * total * (kC2 * 4), kC2 * 4, g0, total, tid);
+      }
+    }
+    if constexpr (MID) {
+      __syncthreads();
+      continue;
     }
     // the top Gaussian and the outputs
     float *bufA = S.u + kBufA;
@@ -599,6 +624,18 @@ static int levels_grid(int64_t tiles) {
 }
 
 }  // namespace cgl
+
+// The backward's forward pass (cglow_levels_bwd.hip): every step's output into zmid, in the MID
+// layout above.  xin null: the measurement form; else the flow form (enc = y, N = 1), as
+// cglow_forward_mid.
+int cglow_levels_forward_mid(const float *pe, const float *glow, int K, int L, const float *enc, int64_t enc_rs,
+                             const float *x, int64_t x_rs, int B, int N, const float *xin, float *zmid,
+                             hipStream_t st) {
+  const int grid = cgl::levels_grid(((int64_t)B * N + cgl::kTileP - 1) / cgl::kTileP);
+  cgl::cglow_levels_kernel<true><<<grid, cgl::kThreads, 0, st>>>(pe, glow, nullptr, enc, enc_rs, x, x_rs, B, N, nullptr, 0,
+                                                                xin, zmid, 1.0f, K, L);
+  return launch_status("cglow_levels_forward_mid");
+}
 }  // namespace nfdpf
 
 using namespace nfdpf;
@@ -620,7 +657,7 @@ extern "C" int nfdpf_cglow_levels_measurement(const float *pe_params, const floa
   NFDPF_REQUIRE(B >= 0 && N >= 1, "nfdpf_cglow_levels_measurement: bad sizes");
   if (B == 0) return NFDPF_OK;
   const int grid = levels_grid(((int64_t)B * N + kTileP - 1) / kTileP);
-  cglow_levels_kernel<<<grid, kThreads, 0, as_stream(stream)>>>(pe_params, glow_params, top, enc, enc_rs, x, x_rs, B, N,
+  cglow_levels_kernel<false><<<grid, kThreads, 0, as_stream(stream)>>>(pe_params, glow_params, top, enc, enc_rs, x, x_rs, B, N,
                                                                  lik, lik_rs, nullptr, nullptr, 1.0f, K, L);
   return launch_status("nfdpf_cglow_levels_measurement");
 }
@@ -633,7 +670,7 @@ extern "C" int nfdpf_cglow_levels_flow(const float *glow_params, int K, int L, c
   if (M == 0) return NFDPF_OK;
   // B = M rows of N = 1 (y row m is sample m), the condition x given, out_sign -1: nll
   const int grid = levels_grid((M + kTileP - 1) / kTileP);
-  cglow_levels_kernel<<<grid, kThreads, 0, as_stream(stream)>>>(glow_params, glow_params, top, y, kE, nullptr, 0, (int)M,
+  cglow_levels_kernel<false><<<grid, kThreads, 0, as_stream(stream)>>>(glow_params, glow_params, top, y, kE, nullptr, 0, (int)M,
                                                                  1, nll, 1, x, z, -1.0f, K, L);
   return launch_status("nfdpf_cglow_levels_flow");
 }

@@ -53,4 +53,11 @@ constexpr int64_t levels_size(int K, int L, bool top) {
 static_assert(levels_size(1, 2, true) == 30000 && levels_size(2, 2, true) == 59148, "parameter counts at L = 2");
 
 }  // namespace cgl
+
+// cglow_levels.hip, for the backward (cglow_levels_bwd.hip): one forward launch that leaves every
+// step's output in zmid -- the K level-1 outputs [k][M][192], then at L = 2 the level-2 inputs /
+// outputs [k][M][96], k = 0 .. K (k = K the final z).  Arguments as cglow_forward_mid.
+int cglow_levels_forward_mid(const float *pe, const float *glow, int K, int L, const float *enc, int64_t enc_rs,
+                             const float *x, int64_t x_rs, int B, int N, const float *xin, float *zmid,
+                             hipStream_t st);
 }  // namespace nfdpf

@@ -393,8 +393,9 @@ class _CglowRunner:
 
 class _CglowLevelsRunner(_CglowRunner):
     """_CglowRunner for the configurations its kernel does not take (L = 2 and / or learn_top):
-    the levels kernel forward (csrc/cglow_levels.hip); no HIP backward -- the bounded PyTorch
-    recompute differentiates torch_forward_raw."""
+    the levels kernel forward (csrc/cglow_levels.hip) and the HIP backward of
+    csrc/cglow_levels_bwd.hip (nfdpf_cglow_levels_measurement_backward); NFDPF_HIP_BACKWARD=0
+    keeps the bounded PyTorch recompute of torch_forward_raw, for comparison."""
 
     def hip(self, enc, x):
         from nfdpf.pack import cglow_levels_tensors
@@ -406,7 +407,24 @@ class _CglowLevelsRunner(_CglowRunner):
                                               learn_top=g.learn_top),)
 
     def hip_backward(self, enc, x, gouts):
-        return None
+        """d/d(enc, x, encoder and CGLOW parameters) on nfdpf_cglow_levels_measurement_backward;
+        None (recompute) outside the configurations csrc/cglow_levels_bwd.hip is built for."""
+        from nfdpf.pack import blob_param_grads, cglow_levels_tensors
+        m = self.model
+        g = m.CGLOW
+        K, L = g.flow.K, g.flow.L
+        if enc.dim() != 2 or enc.shape[-1] != 192 or x.dim() != 3 or x.shape[-1] != 2 \
+                or not g.levels_kernel_supported() or not _ops.cglow_levels_backward_supported(K, L):
+            return None
+        pe = blob(m, "pe", m.particle_encoder, lambda: encoder_tensors(m.particle_encoder), x.device)
+        glow = blob(m, "glow_levels", g, lambda: cglow_levels_tensors(g), x.device)
+        gl = gouts[0] if gouts[0] is not None else torch.zeros(x.shape[:2], device=x.device)
+        g_enc, gx, g_glow, g_pe = _ops.cglow_levels_measurement_backward(pe, glow, enc.float(), x.float(), gl.float(),
+                                                                         K=K, L=L, learn_top=g.learn_top)
+        pe_params, gl_params = list(m.particle_encoder.parameters()), list(g.parameters())
+        res = blob_param_grads(m, "pe_grad", pe_params, lambda get: encoder_tensors(m.particle_encoder, get), g_pe)
+        res += blob_param_grads(m, "glow_levels_grad", gl_params, lambda get: cglow_levels_tensors(g, get), g_glow)
+        return (g_enc.to(enc.dtype), gx.to(x.dtype)), res
 
 
 class measurement_model_cglow(nn.Module):
@@ -425,7 +443,7 @@ class measurement_model_cglow(nn.Module):
         if self.CGLOW.kernel_supported():
             runner = _CglowRunner(self)
         elif self.CGLOW.levels_kernel_supported():
-            # L = 2 and / or learn_top: csrc/cglow_levels.hip, gradients through the bounded recompute
+            # L = 2 and / or learn_top: csrc/cglow_levels.hip, gradients on csrc/cglow_levels_bwd.hip
             runner = _CglowLevelsRunner(self)
         else:
             raise NfdpfError("measurement_model_cglow: the HIP kernels are built for the reference's default CGLOW "

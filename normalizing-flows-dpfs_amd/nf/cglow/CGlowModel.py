@@ -7,9 +7,10 @@ Gaussian log-prob, CGlowModel.py:167-176) -- runs as one HIP kernel (csrc/cglow.
 nfdpf_cglow_flow) for the configuration the reference's flags give (K in 1..4, L = 1, x_size =
 y_size = (3, 8, 8), learn_top off) and returns the reference's (z, nll); with L = 2 (Split2d and
 a second level on 24 x 2 x 2) and / or learn_top it runs as one launch of csrc/cglow_levels.hip
-(nfdpf_cglow_levels_flow).  Under autograd the backward is the HIP one (csrc/cglow_bwd.hip) at
-L = 1 without learn_top; otherwise it differentiates ``torch_forward``, a PyTorch restatement of
-the same math run on the saved inputs (nfdpf.autograd; the forward value is the kernel's).
+(nfdpf_cglow_levels_flow).  Under autograd the backward is the HIP one: csrc/cglow_bwd.hip at
+L = 1 without learn_top, csrc/cglow_levels_bwd.hip at L = 2 and / or with learn_top.  With
+NFDPF_HIP_BACKWARD=0 it differentiates ``torch_forward`` instead, a PyTorch restatement of the
+same math run on the saved inputs (nfdpf.autograd; the forward value is the kernel's).
 ``reverse=True`` (sampling; the DPF never calls it) runs the layers' PyTorch reverse."""
 import numpy as np
 import torch
@@ -114,8 +115,9 @@ class _FlowRunner:
 
 class _LevelsFlowRunner(_FlowRunner):
     """The runner of the configurations _FlowRunner's kernel does not take (L = 2 and / or
-    learn_top): the levels kernel forward (csrc/cglow_levels.hip); no HIP backward -- the
-    recompute path differentiates torch_forward, which is general in L and learn_top."""
+    learn_top): the levels kernel forward (csrc/cglow_levels.hip) and the HIP backward of
+    csrc/cglow_levels_bwd.hip; NFDPF_HIP_BACKWARD=0 differentiates torch_forward, which is
+    general in L and learn_top, instead."""
 
     def hip(self, x, y):
         from nfdpf import ops
@@ -125,7 +127,21 @@ class _LevelsFlowRunner(_FlowRunner):
         return ops.cglow_levels_flow(glow, x, y, K=m.flow.K, L=m.flow.L, learn_top=m.learn_top)
 
     def hip_backward(self, x, y, gouts):
-        return None
+        """d/d(x, y, parameters) on nfdpf_cglow_levels_flow_backward (csrc/cglow_levels_bwd.hip);
+        None (recompute) outside the configurations that kernel is built for."""
+        from nfdpf import ops
+        from nfdpf.pack import blob, blob_param_grads, cglow_levels_tensors
+        m = self.model
+        K, L = m.flow.K, m.flow.L
+        if not m.levels_kernel_supported() or not ops.cglow_levels_backward_supported(K, L) \
+                or tuple(x.shape[1:]) != (3, 8, 8) or tuple(y.shape) != tuple(x.shape):
+            return None
+        glow = blob(m, "glow_levels", m, lambda: cglow_levels_tensors(m), x.device)
+        g_z, g_nll = gouts
+        gx, gy, g_glow = ops.cglow_levels_flow_backward(glow, x, y, g_z, g_nll, K=K, L=L, learn_top=m.learn_top)
+        res = blob_param_grads(m, "glow_levels_grad", list(m.parameters()), lambda get: cglow_levels_tensors(m, get),
+                               g_glow)
+        return (gx, gy), res
 
 
 class CondGlowModel(nn.Module):

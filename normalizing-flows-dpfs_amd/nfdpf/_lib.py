@@ -125,6 +125,13 @@ SIGNATURES = {
                                                c_void_p, c_int64, c_int, c_int, c_void_p, c_int64, c_void_p]),
     "nfdpf_cglow_levels_flow": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
                                         c_void_p, c_void_p]),
+    "nfdpf_cglow_levels_backward_workspace": (c_int64, [c_int64, c_int, c_int]),
+    "nfdpf_cglow_levels_measurement_backward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                                                        c_int64, c_void_p, c_int64, c_int, c_int, c_void_p, c_int64,
+                                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nfdpf_cglow_levels_flow_backward": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64,
+                                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                 c_void_p]),
     "nfdpf_cglow_backward_workspace": (c_int64, [c_int64]),
     "nfdpf_cglow_backward_workspace_k": (c_int64, [c_int64, c_int]),
     "nfdpf_cglow_measurement_backward": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_int64,

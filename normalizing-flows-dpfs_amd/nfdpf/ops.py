@@ -569,6 +569,67 @@ def cglow_levels_flow(glow_blob, x, y, K=1, L=1, learn_top=False):
     return z, nll
 
 
+def cglow_levels_backward_supported(K, L) -> bool:
+    """True where csrc/cglow_levels_bwd.hip is built for (K, L): K in 1..4, L in 1..2."""
+    return int(lib().nfdpf_cglow_levels_backward_workspace(0, int(K), int(L))) >= 0
+
+
+def _levels_backward_ws(M, K, L, device, what):
+    nb = int(lib().nfdpf_cglow_levels_backward_workspace(int(M), int(K), int(L)))
+    if nb < 0:
+        raise NfdpfError(f"{what}: the HIP backward is not built for K = {K}, L = {L}")
+    return torch.empty(max(1, nb // 4), device=device, dtype=f32)
+
+
+def cglow_levels_measurement_backward(pe_blob, glow_blob, enc, x, g_lik, K=1, L=1, learn_top=False):
+    """Backward of cglow_levels_measurement (raw lik, no row-max shift): enc [B, 192], x [B, N, 2],
+    g_lik [B, N] -> (g_enc [B, 192], g_x [B, N, 2], g_glow [the levels blob's layout, the tail
+    [new_mean | new_logs] included with learn_top], g_pe [blob])
+    (nfdpf_cglow_levels_measurement_backward)."""
+    require_device(x, "cglow_levels_measurement_backward")
+    B, N, _ = x.shape
+    x, enc, g_lik = _c(x), _c(enc), _c(g_lik)
+    if enc.shape[-1] != 192:
+        raise NfdpfError("cglow_levels_measurement_backward: frame encodings must be 192 wide (--hiddensize 192)")
+    glow_blob, top = _levels_blob(glow_blob, K, L, learn_top, "cglow_levels_measurement_backward")
+    ws = _levels_backward_ws(B * N, K, L, x.device, "cglow_levels_measurement_backward")
+    gx = torch.empty_like(x)
+    gy = torch.empty((B * N, 192), device=x.device, dtype=f32)
+    g_glow = torch.empty_like(glow_blob)
+    g_pe = torch.empty_like(pe_blob)
+    check(lib().nfdpf_cglow_levels_measurement_backward(ptr(pe_blob), ptr(glow_blob), int(K), int(L), top, ptr(enc),
+                                                        enc.stride(0), ptr(x), x.stride(0), B, N, ptr(g_lik),
+                                                        g_lik.stride(0), ptr(gx), ptr(gy), ptr(g_glow), ptr(g_pe),
+                                                        ptr(ws), stream_ptr(x.device)),
+          "nfdpf_cglow_levels_measurement_backward")
+    return gy.view(B, N, 192).sum(1), gx, g_glow, g_pe
+
+
+def cglow_levels_flow_backward(glow_blob, x, y, g_z, g_nll, K=1, L=1, learn_top=False):
+    """Backward of cglow_levels_flow: x, y [M,3,8,8], g_z of the final z's shape (or None), g_nll
+    [M] (or None) -> (g_x, g_y [M,3,8,8], g_glow [the levels blob's layout])
+    (nfdpf_cglow_levels_flow_backward)."""
+    require_device(x, "cglow_levels_flow_backward")
+    M = x.shape[0]
+    x, y = _c(x), _c(y)
+    glow_blob, top = _levels_blob(glow_blob, K, L, learn_top, "cglow_levels_flow_backward")
+    ws = _levels_backward_ws(M, K, L, x.device, "cglow_levels_flow_backward")
+    nz = 96 if int(L) == 2 else 192
+    if g_z is not None and g_z.numel() != M * nz:
+        raise NfdpfError(f"cglow_levels_flow_backward: g_z must hold {nz} floats per sample "
+                         f"(got {tuple(g_z.shape)} for M = {M})")
+    g_nll = _c(g_nll) if g_nll is not None else torch.zeros((M,), device=x.device, dtype=f32)
+    g_z = _c(g_z) if g_z is not None else None
+    gx = torch.empty_like(x)
+    gy = torch.empty_like(y)
+    g_glow = torch.empty_like(glow_blob)
+    check(lib().nfdpf_cglow_levels_flow_backward(ptr(glow_blob), int(K), int(L), top, ptr(x), ptr(y), int(M),
+                                                 ptr(g_z) if g_z is not None else None, ptr(g_nll), ptr(gx), ptr(gy),
+                                                 ptr(g_glow), ptr(ws), stream_ptr(x.device)),
+          "nfdpf_cglow_levels_flow_backward")
+    return gx, gy, g_glow
+
+
 def particle_init(start_xy, B, N, width, true_state, seed, row_base=0, device=None):
     """particle_initialization (utils.py:46-62), device RNG -> (x [B,N,2], logw [B,N])."""
     device = device if device is not None else start_xy.device
