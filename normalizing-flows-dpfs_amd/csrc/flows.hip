@@ -149,9 +149,9 @@ extern "C" int nfdpf_cond_stack(const float *params, int n_flows, int dim, int o
 extern "C" int nfdpf_maf_stack(const float *params, int n_flows, int dim, int hidden,
                                const float *x, int64_t rows, int inverse, float *out,
                                float *logdet, void *stream) {
-  NFDPF_REQUIRE(params && x && out && logdet, "nfdpf_maf_stack: null pointer");
   NFDPF_REQUIRE(n_flows >= 0 && rows >= 0, "nfdpf_maf_stack: bad sizes");
-  if (rows == 0) return NFDPF_OK;
+  if (rows == 0) return NFDPF_OK;  // before the pointer check: an empty tensor's data pointer is null
+  NFDPF_REQUIRE(params && x && out && logdet, "nfdpf_maf_stack: null pointer");
   const dim3 g((unsigned)((rows + kStackBlock - 1) / kStackBlock));
   hipStream_t st = as_stream(stream);
   const bool inv = inverse != 0;

@@ -276,7 +276,8 @@ extern "C" int64_t nfdpf_maf_stack_backward_workspace(int n_flows, int dim, int 
 extern "C" int nfdpf_maf_stack_backward(const float *params, int n_flows, int dim, int hidden, const float *x,
                                         int64_t rows, int inverse, const float *g_out, const float *g_logdet,
                                         float *g_x, float *g_params, void *workspace, void *stream) {
-  NFDPF_REQUIRE(params && x && g_x && g_params && workspace, "nfdpf_maf_stack_backward: null pointer");
+  // x and g_x are checked after the rows == 0 return: an empty tensor's data pointer is null
+  NFDPF_REQUIRE(params && g_params && workspace, "nfdpf_maf_stack_backward: null pointer");
   NFDPF_REQUIRE(hidden == 8 && (dim == 2 || dim == 4), "nfdpf_maf_stack_backward: dim 2 or 4, hidden 8");
   NFDPF_REQUIRE(n_flows >= 1 && n_flows <= kMafMaxFlows && rows >= 0, "nfdpf_maf_stack_backward: bad sizes");
   const size_t lds = sizeof(float) * (size_t)n_flows * (dim == 2 ? maf_fac<2, 8>(2) : maf_fac<4, 8>(4)) * kMafRows;
@@ -288,6 +289,7 @@ extern "C" int nfdpf_maf_stack_backward(const float *params, int n_flows, int di
       return launch_status("nfdpf_maf_stack_backward (memset)");
     return NFDPF_OK;
   }
+  NFDPF_REQUIRE(x && g_x, "nfdpf_maf_stack_backward: null pointer");
   hipStream_t st = as_stream(stream);
   float *ws = (float *)workspace;
   return dim == 2 ? maf_bwd_launch<2>(inverse != 0, st, params, n_flows, x, rows, g_out, g_logdet, g_x, g_params, ws)
