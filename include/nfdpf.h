@@ -333,6 +333,30 @@ NFDPF_API int nfdpf_cglow_levels_measurement(const float *pe_params, const float
 NFDPF_API int nfdpf_cglow_levels_flow(const float *glow_params, int K, int L, const float *top, const float *x,
                                       const float *y, int64_t M, float *z, float *nll, void *stream);
 
+/* The two entry points above at other hidden sizes of the conditional GLOW and / or another
+ * number of bins (the reference's --x_hidden_channels xh, --x_hidden_size xs,
+ * --y_hidden_channels yh, --y_bins); forward only, one launch per call, no workspace
+ * (csrc/cglow_wide.hip).  The supported set is every combination of xh in {8, 16}, xs in
+ * {16, 32}, yh in {8, 16, 32} (the list: csrc/cglow_widths.hpp; nfdpf_cglow_wide_supported
+ * answers 1 on it, else 0) at K in 1..4, L in 1..2, either learn_top.
+ *   glow_params: the layout of nfdpf_cglow_levels_measurement with the three sizes in place of
+ *     8 / 16 / 8 (packed by nfdpf.pack.cglow_levels_tensors, which is general in them);
+ *     nfdpf_cglow_wide_params_size counts its floats, -1 for K, L or a size outside the set.
+ *   logdet0: -log(y_bins) * 192, computed in double and rounded to float once by the caller
+ *     (-1064.674... at 256 bins); must be finite.
+ *   other arguments, z and nll as nfdpf_cglow_levels_measurement / nfdpf_cglow_levels_flow.
+ * K, L or the sizes outside the set: NFDPF_EINVAL, nothing launched.  B = 0 or M = 0: OK,
+ * nothing launched. */
+NFDPF_API int nfdpf_cglow_wide_supported(int xh, int xs, int yh);
+NFDPF_API int64_t nfdpf_cglow_wide_params_size(int K, int L, int learn_top, int xh, int xs, int yh);
+NFDPF_API int nfdpf_cglow_wide_measurement(const float *pe_params, const float *glow_params, int K, int L,
+                                           const float *top, const float *enc, int64_t enc_rs, const float *x,
+                                           int64_t x_rs, int B, int N, float *lik, int64_t lik_rs, int xh, int xs,
+                                           int yh, float logdet0, void *stream);
+NFDPF_API int nfdpf_cglow_wide_flow(const float *glow_params, int K, int L, const float *top, const float *x,
+                                    const float *y, int64_t M, float *z, float *nll, int xh, int xs, int yh,
+                                    float logdet0, void *stream);
+
 /* Backward of the two CGLOW entry points nfdpf_cglow_measurement / nfdpf_cglow_flow (training; the autograd
  * gradient of nf/cglow/modules.py + CGlowModel.py:167-176, d log|det W| / dW = W^-T).
  * Deterministic (fixed-order per-workgroup partials in the workspace, reduced in order).

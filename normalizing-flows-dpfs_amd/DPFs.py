@@ -26,7 +26,8 @@ from model.models import (build_conditional_glow, build_conditional_nf, build_de
                           measurement_model_cglow, measurement_model_cnf, measurement_model_cosine_distance,
                           measurement_model_Gaussian, measurement_model_NN, motion_update, nf_dynamic_model,
                           proposal_likelihood)
-from nfdpf._lib import NfdpfError, meas_width_supported, require_meas_width
+from nfdpf._lib import (NfdpfError, cglow_widths_supported, meas_width_supported, require_cglow_widths,
+                        require_meas_width)
 from nfdpf.engine import FilterConfig, FilterEngine, ShardInfo
 from nfdpf.gradsync import GradBucket, global_mean, sharded_supervised_loss, world_size
 from resamplers.resamplers import resampler
@@ -65,6 +66,9 @@ class DPF(nn.Module):
             # (the CGLOW kernels take one or two levels: refuse here, not inside the first step)
             raise NfdpfError(f"DPF: the CGLOW measurement's HIP kernels are built for num_levels L in 1..2 "
                              f"(got -L {args.num_levels})")
+        if args.measurement == "CGLOW":
+            # (and the hidden sizes of csrc/cglow_widths.hpp; --x_bins is not read, as in the reference)
+            require_cglow_widths(*self._cglow_widths(args), "DPF")
         self.state_dim = 2  # particles are 2-D positions (DPFs.py:31)
         self.lr = args.lr
         self.alpha = args.alpha
@@ -178,10 +182,16 @@ class DPF(nn.Module):
             force_resample=getattr(a, "force_resample", False),
             dyn_flow=getattr(a, "NF_dyn_flow", "RealNVP"))
 
+    @staticmethod
+    def _cglow_widths(a):
+        return (getattr(a, "x_hidden_channels", 8), getattr(a, "x_hidden_size", 16),
+                getattr(a, "y_hidden_channels", 8))
+
     def _fused_supported(self):
         if self.measurement == "CGLOW":
             return (self.hidden_size == 192 and 1 <= getattr(self.param, "flow_depth", 1) <= 4
-                    and 1 <= getattr(self.param, "num_levels", 1) <= 2)
+                    and 1 <= getattr(self.param, "num_levels", 1) <= 2
+                    and cglow_widths_supported(*self._cglow_widths(self.param)))
         return self.measurement in ("cos", "CRNVP", "NN", "gaussian") and \
             meas_width_supported(self.measurement, self.hidden_size)
 

@@ -427,6 +427,24 @@ class _CglowLevelsRunner(_CglowRunner):
         return (g_enc.to(enc.dtype), gx.to(x.dtype)), res
 
 
+class _CglowWideRunner(_CglowRunner):
+    """_CglowRunner at the hidden sizes of csrc/cglow_widths.hpp other than 8 / 16 / 8 and at bin
+    counts other than 256: the width-general forward kernel (csrc/cglow_wide.hip).  No HIP backward
+    at these sizes: the bounded PyTorch recompute of torch_forward_raw gives the gradients."""
+
+    def hip(self, enc, x):
+        from nfdpf.pack import cglow_levels_tensors
+        m = self.model
+        g = m.CGLOW
+        pe = blob(m, "pe", m.particle_encoder, lambda: encoder_tensors(m.particle_encoder), x.device)
+        glow = blob(m, "glow_levels", g, lambda: cglow_levels_tensors(g), x.device)
+        return (_ops.cglow_wide_measurement(pe, glow, enc.float(), x.float(), K=g.flow.K, L=g.flow.L,
+                                            learn_top=g.learn_top, widths=g.hidden_sizes(), y_bins=g.n_bins),)
+
+    def hip_backward(self, enc, x, gouts):
+        return None
+
+
 class measurement_model_cglow(nn.Module):
     """Conditional-GLOW likelihood (model/models.py:280-303)."""
 
@@ -445,9 +463,13 @@ class measurement_model_cglow(nn.Module):
         elif self.CGLOW.levels_kernel_supported():
             # L = 2 and / or learn_top: csrc/cglow_levels.hip, gradients on csrc/cglow_levels_bwd.hip
             runner = _CglowLevelsRunner(self)
+        elif self.CGLOW.wide_kernel_supported():
+            # other hidden sizes or bins: csrc/cglow_wide.hip, gradients by the PyTorch recompute
+            runner = _CglowWideRunner(self)
         else:
-            raise NfdpfError("measurement_model_cglow: the HIP kernels are built for the reference's default CGLOW "
-                             "with flow_depth K in 1..4 and num_levels L in 1..2 (3x8x8, hidden 8 / 16 / 8, 256 bins)")
+            raise NfdpfError("measurement_model_cglow: the HIP kernels are built for the reference's CGLOW with "
+                             "flow_depth K in 1..4, num_levels L in 1..2, 3x8x8 inputs, x_hidden_channels in {8, 16}, "
+                             "x_hidden_size in {16, 32}, y_hidden_channels in {8, 16, 32} and finite y_bins > 0")
         lik = _ag.apply(runner, (encodings, update_particles), list(self.parameters()))[0]
         return lik - lik.max(dim=-1, keepdim=True)[0]
 

@@ -7,8 +7,12 @@ Gaussian log-prob, CGlowModel.py:167-176) -- runs as one HIP kernel (csrc/cglow.
 nfdpf_cglow_flow) for the configuration the reference's flags give (K in 1..4, L = 1, x_size =
 y_size = (3, 8, 8), learn_top off) and returns the reference's (z, nll); with L = 2 (Split2d and
 a second level on 24 x 2 x 2) and / or learn_top it runs as one launch of csrc/cglow_levels.hip
-(nfdpf_cglow_levels_flow).  Under autograd the backward is the HIP one: csrc/cglow_bwd.hip at
-L = 1 without learn_top, csrc/cglow_levels_bwd.hip at L = 2 and / or with learn_top.  With
+(nfdpf_cglow_levels_flow); at the other hidden sizes of csrc/cglow_widths.hpp
+(--x_hidden_channels / --x_hidden_size / --y_hidden_channels) or another --y_bins as one launch of
+csrc/cglow_wide.hip (nfdpf_cglow_wide_flow), forward only.  --x_bins is not read, as in the
+reference.  Under autograd the backward is the HIP one: csrc/cglow_bwd.hip at
+L = 1 without learn_top, csrc/cglow_levels_bwd.hip at L = 2 and / or with learn_top; at the
+sizes and bins of csrc/cglow_wide.hip it is the PyTorch recompute below.  With
 NFDPF_HIP_BACKWARD=0 it differentiates ``torch_forward`` instead, a PyTorch restatement of the
 same math run on the saved inputs (nfdpf.autograd; the forward value is the kernel's).
 ``reverse=True`` (sampling; the DPF never calls it) runs the layers' PyTorch reverse."""
@@ -144,6 +148,30 @@ class _LevelsFlowRunner(_FlowRunner):
         return (gx, gy), res
 
 
+class _WideFlowRunner(_FlowRunner):
+    """The runner of the hidden sizes of csrc/cglow_widths.hpp other than 8 / 16 / 8, and of bin
+    counts other than 256: the width-general forward kernel (csrc/cglow_wide.hip).  There is no
+    HIP backward at these sizes: gradients come from the PyTorch recompute of torch_forward,
+    which is general in the sizes and in y_bins, bounded to RECOMPUTE_ROWS samples like the
+    measurement form's (model.models._CglowRunner)."""
+
+    RECOMPUTE_ROWS = 16384
+
+    def recompute_limit(self, x, y):
+        return self.RECOMPUTE_ROWS, x.shape[0]
+
+    def hip(self, x, y):
+        from nfdpf import ops
+        from nfdpf.pack import blob, cglow_levels_tensors
+        m = self.model
+        glow = blob(m, "glow_levels", m, lambda: cglow_levels_tensors(m), x.device)
+        return ops.cglow_wide_flow(glow, x, y, K=m.flow.K, L=m.flow.L, learn_top=m.learn_top,
+                                   widths=m.hidden_sizes(), y_bins=m.n_bins)
+
+    def hip_backward(self, x, y, gouts):
+        return None
+
+
 class CondGlowModel(nn.Module):
     def __init__(self, args):
         super().__init__()
@@ -162,13 +190,17 @@ class CondGlowModel(nn.Module):
             return self.new_mean, self.new_logs
         return torch.zeros_like(self.new_mean), torch.zeros_like(self.new_mean)
 
+    def hidden_sizes(self):
+        """(x_hidden_channels, x_hidden_size, y_hidden_channels) the model was built with."""
+        return _hidden_sizes(self.flow)
+
     def kernel_supported(self) -> bool:
         """The configuration csrc/cglow.hip is built for: the reference's defaults
         (arguments.py:61-70) with flow_depth K in 1..4: L = 1, 3x8x8 x and y, hidden 8 / 16 / 8,
         learn_top off."""
         f = self.flow
         return (1 <= f.K <= 4 and f.L == 1 and not self.learn_top and float(self.n_bins) == 256.0
-                and list(f.output_shapes[-1][1:]) == [12, 4, 4])
+                and list(f.output_shapes[-1][1:]) == [12, 4, 4] and _hidden_sizes(f) == (8, 16, 8))
 
     def levels_kernel_supported(self) -> bool:
         """The configurations csrc/cglow_levels.hip is built for: K in 1..4, L in 1..2, any
@@ -178,10 +210,23 @@ class CondGlowModel(nn.Module):
                 and list(f.output_shapes[-1][1:]) == ([12, 4, 4] if f.L == 1 else [24, 2, 2])
                 and _hidden_sizes(f) == (8, 16, 8))
 
+    def wide_kernel_supported(self) -> bool:
+        """The configurations csrc/cglow_wide.hip is built for: K in 1..4, L in 1..2, any
+        learn_top, 3x8x8 x and y, hidden sizes in the set of csrc/cglow_widths.hpp (every
+        combination of x_hidden_channels in {8, 16}, x_hidden_size in {16, 32}, y_hidden_channels
+        in {8, 16, 32}), any finite y_bins > 0.  x_bins is not read, as in the reference."""
+        from nfdpf._lib import cglow_widths_supported
+        f = self.flow
+        nb = float(self.n_bins)
+        return (1 <= f.K <= 4 and 1 <= f.L <= 2 and np.isfinite(nb) and nb > 0
+                and list(f.output_shapes[-1][1:]) == ([12, 4, 4] if f.L == 1 else [24, 2, 2])
+                and cglow_widths_supported(*_hidden_sizes(f)))
+
     def forward(self, x=0.0, y=None, eps_std=1.0, reverse=False):
         """reverse=False: (z, nll) of y given the condition x (CGlowModel.py:167-176), on the
         HIP kernel: csrc/cglow.hip at L = 1 without learn_top, csrc/cglow_levels.hip at L = 2
-        and / or with learn_top (z is the final z, [M, 24, 2, 2] at L = 2).
+        and / or with learn_top (z is the final z, [M, 24, 2, 2] at L = 2), csrc/cglow_wide.hip
+        at hidden sizes other than 8 / 16 / 8 or y_bins other than 256.
         reverse=True: a sample (or the inverse of a given y) and its log-det
         (:178-184), PyTorch (off the DPF path)."""
         if reverse:
@@ -194,9 +239,12 @@ class CondGlowModel(nn.Module):
             runner = _FlowRunner(self)
         elif self.levels_kernel_supported():
             runner = _LevelsFlowRunner(self)
+        elif self.wide_kernel_supported():
+            runner = _WideFlowRunner(self)
         else:
             raise NfdpfError("CondGlowModel.forward: the HIP kernels are built for K in 1..4, L in 1..2, 3x8x8 "
-                             "inputs, hidden sizes 8 / 16 / 8 and 256 bins")
+                             "inputs, x_hidden_channels in {8, 16}, x_hidden_size in {16, 32}, y_hidden_channels "
+                             "in {8, 16, 32} and finite y_bins > 0")
         z, nll = _ag.apply(runner, (x.float().contiguous(), y.float().contiguous()), list(self.parameters()))
         return z, nll
 

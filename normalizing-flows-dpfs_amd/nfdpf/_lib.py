@@ -125,6 +125,13 @@ SIGNATURES = {
                                                c_void_p, c_int64, c_int, c_int, c_void_p, c_int64, c_void_p]),
     "nfdpf_cglow_levels_flow": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
                                         c_void_p, c_void_p]),
+    "nfdpf_cglow_wide_supported": (c_int, [c_int, c_int, c_int]),
+    "nfdpf_cglow_wide_params_size": (c_int64, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "nfdpf_cglow_wide_measurement": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int64,
+                                             c_void_p, c_int64, c_int, c_int, c_void_p, c_int64, c_int, c_int, c_int,
+                                             c_float, c_void_p]),
+    "nfdpf_cglow_wide_flow": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
+                                      c_void_p, c_int, c_int, c_int, c_float, c_void_p]),
     "nfdpf_cglow_levels_backward_workspace": (c_int64, [c_int64, c_int, c_int]),
     "nfdpf_cglow_levels_measurement_backward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
                                                         c_int64, c_void_p, c_int64, c_int, c_int, c_void_p, c_int64,
@@ -197,6 +204,30 @@ def require_meas_width(kind: str, E: int, what: str):
     if not meas_width_supported(kind, E):
         raise NfdpfError(f"{what}: the '{kind}' measurement is not built for frame-encoding width {E} "
                          f"(--hiddensize); supported widths: {', '.join(map(str, meas_widths(kind)))}")
+
+
+def cglow_widths_supported(xh: int, xs: int, yh: int) -> bool:
+    """Is (x_hidden_channels, x_hidden_size, y_hidden_channels) in the set the CGLOW kernels
+    take?  The library holds the list (csrc/cglow_widths.hpp); this asks it."""
+    return bool(lib().nfdpf_cglow_wide_supported(int(xh), int(xs), int(yh)))
+
+
+def cglow_widths():
+    """The three lists the library is built for (for messages), asked of the library."""
+    if "cglow" not in _widths:
+        rng = range(1, 257)
+        _widths["cglow"] = ([v for v in rng if cglow_widths_supported(v, 16, 8)],
+                            [v for v in rng if cglow_widths_supported(8, v, 8)],
+                            [v for v in rng if cglow_widths_supported(8, 16, v)])
+    return _widths["cglow"]
+
+
+def require_cglow_widths(xh: int, xs: int, yh: int, what: str):
+    if not cglow_widths_supported(xh, xs, yh):
+        a, b, c = cglow_widths()
+        raise NfdpfError(f"{what}: the CGLOW measurement is not built for hidden sizes {xh} / {xs} / {yh} "
+                         f"(--x_hidden_channels / --x_hidden_size / --y_hidden_channels); supported: every "
+                         f"combination of x_hidden_channels in {a}, x_hidden_size in {b}, y_hidden_channels in {c}")
 
 
 def load(path: str = LIB_PATH):

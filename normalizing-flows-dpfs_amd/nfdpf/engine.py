@@ -494,8 +494,13 @@ class FilterEngine:
             g = m.cglow_measurement
             if g.kernel_supported():
                 meas = blob(m, "glow", g, lambda: cglow_tensors(g), dev)
-            else:  # L = 2 and / or learn_top: the levels kernel's layout (csrc/cglow_levels.hpp)
+            elif g.levels_kernel_supported() or g.wide_kernel_supported():
+                # L = 2 and / or learn_top: the levels kernel's layout (csrc/cglow_levels.hpp); other
+                # hidden sizes or bins: the same layout at those sizes (csrc/cglow_widths.hpp)
                 meas = blob(m, "glow_levels", g, lambda: cglow_levels_tensors(g), dev)
+            else:
+                raise L.NfdpfError("FilterEngine: this CGLOW configuration has no HIP kernel (K in 1..4, L in 1..2, "
+                                   "hidden sizes of csrc/cglow_widths.hpp, finite y_bins > 0)")
         return dyn, cond, pe, meas
 
     # -- main loop --------------------------------------------------------------------------
@@ -538,7 +543,12 @@ class FilterEngine:
         if wide:
             L.require_meas_width(c.measurement, E, "FilterEngine.run")
         external = self._external = c.measurement == "CGLOW" or wide
-        glow_levels = c.measurement == "CGLOW" and not self.m.cglow_measurement.kernel_supported()
+        # CGLOW's kernel by configuration: cglow.hip, else cglow_levels.hip, else cglow_wide.hip
+        glow_levels = glow_wide = False
+        if c.measurement == "CGLOW" and not self.m.cglow_measurement.kernel_supported():
+            glow_levels = self.m.cglow_measurement.levels_kernel_supported()
+            glow_wide = not glow_levels
+            glow_widths = self.m.cglow_measurement.hidden_sizes()
         N = c.N
         shard = shard or ShardInfo(1, 0, B, 0, None)
         if shard.world == 1 and shard.B_global != B:
@@ -871,6 +881,11 @@ class FilterEngine:
                     g = self.m.cglow_measurement
                     ops.cglow_levels_measurement(pe, meas, enc[:, t], hx[:, t], K=g.flow.K, L=g.flow.L,
                                                  learn_top=g.learn_top, out=lik_ext)
+                elif glow_wide:  # other hidden sizes or bins (the same blob layout at those sizes)
+                    g = self.m.cglow_measurement
+                    ops.cglow_wide_measurement(pe, meas, enc[:, t], hx[:, t], K=g.flow.K, L=g.flow.L,
+                                               learn_top=g.learn_top, widths=glow_widths, y_bins=g.n_bins,
+                                               out=lik_ext)
                 else:
                     ops.cglow_measurement(pe, meas, enc[:, t], hx[:, t], K=self.m.cglow_measurement.flow.K,
                                           out=lik_ext)

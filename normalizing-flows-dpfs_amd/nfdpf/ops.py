@@ -7,12 +7,13 @@ no synchronisation.
 from __future__ import annotations
 
 import functools
+import math
 from typing import Optional
 
 import torch
 
 from . import _lib as L
-from ._lib import NfdpfError, check, lib, ptr, require_device, stream_ptr
+from ._lib import NfdpfError, check, lib, ptr, require_cglow_widths, require_device, stream_ptr
 
 f32 = torch.float32
 
@@ -566,6 +567,75 @@ def cglow_levels_flow(glow_blob, x, y, K=1, L=1, learn_top=False):
     nll = torch.empty((M,), device=x.device, dtype=f32)
     check(lib().nfdpf_cglow_levels_flow(ptr(glow_blob), int(K), int(L), top, ptr(x), ptr(y), int(M), ptr(z), ptr(nll),
                                         stream_ptr(x.device)), "nfdpf_cglow_levels_flow")
+    return z, nll
+
+
+def _wide_blob(glow_blob, K, L, learn_top, widths, y_bins, what):
+    """Check a cglow_levels_tensors blob against (K, L, learn_top) and the hidden sizes
+    ``widths`` = (x_hidden_channels, x_hidden_size, y_hidden_channels); -> (blob, pointer to its
+    [new_mean | new_logs] tail or None, the three sizes, logdet0 = -log(y_bins) 192 in double)."""
+    try:
+        xh, xs, yh = (int(v) for v in widths)
+    except (TypeError, ValueError):
+        raise NfdpfError(f"{what}: widths must be (x_hidden_channels, x_hidden_size, y_hidden_channels), "
+                         f"got {widths!r}") from None
+    if not 1 <= int(K) <= 4 or not 1 <= int(L) <= 2:
+        raise NfdpfError(f"{what}: built for flow_depth K in 1..4 and num_levels L in 1..2 (got K = {K}, L = {L})")
+    require_cglow_widths(xh, xs, yh, what)
+    y_bins = float(y_bins)
+    if not (math.isfinite(y_bins) and y_bins > 0):
+        raise NfdpfError(f"{what}: y_bins must be finite and > 0 (got {y_bins})")
+    n = int(lib().nfdpf_cglow_wide_params_size(int(K), int(L), int(bool(learn_top)), xh, xs, yh))
+    if int(glow_blob.numel()) != n:
+        raise NfdpfError(f"{what}: parameter blob does not match K = {K}, L = {L}, learn_top = {bool(learn_top)}, "
+                         f"hidden sizes {xh} / {xs} / {yh} ({int(glow_blob.numel())} floats, expected {n})")
+    glow_blob = _c(glow_blob)
+    nz = 96 if int(L) == 2 else 192
+    return glow_blob, (ptr(glow_blob[n - 2 * nz:]) if learn_top else None), (xh, xs, yh), -math.log(y_bins) * 192.0
+
+
+def cglow_wide_measurement(pe_blob, glow_blob, enc, x, K=1, L=1, learn_top=False, widths=(8, 16, 8), y_bins=256.0,
+                           out=None):
+    """cglow_levels_measurement at the hidden sizes ``widths`` = (x_hidden_channels,
+    x_hidden_size, y_hidden_channels) of csrc/cglow_widths.hpp and any finite y_bins > 0
+    (nfdpf_cglow_wide_measurement, csrc/cglow_wide.hip; glow_blob from
+    nfdpf.pack.cglow_levels_tensors): enc [B, 192] (rows may be strided), x [B, N, 2] -> raw lik
+    [B, N], no row-max shift."""
+    require_device(x, "cglow_wide_measurement")
+    B, N, _ = x.shape
+    if x.stride(2) != 1 or x.stride(1) != 2:
+        x = x.contiguous()
+    if enc.stride(-1) != 1:
+        enc = enc.contiguous()
+    if enc.shape[-1] != 192:
+        raise NfdpfError("cglow_wide_measurement: frame encodings must be 192 wide (--hiddensize 192)")
+    glow_blob, top, (xh, xs, yh), ld0 = _wide_blob(glow_blob, K, L, learn_top, widths, y_bins, "cglow_wide_measurement")
+    lik = out if out is not None else torch.empty((B, N), device=x.device, dtype=f32)
+    if B * N == 0:  # (empty tensors have no pointer to pass)
+        return lik
+    check(lib().nfdpf_cglow_wide_measurement(ptr(pe_blob), ptr(glow_blob), int(K), int(L), top, ptr(enc),
+                                             enc.stride(0), ptr(x), x.stride(0), B, N, ptr(lik), lik.stride(0),
+                                             xh, xs, yh, ld0, stream_ptr(x.device)), "nfdpf_cglow_wide_measurement")
+    return lik
+
+
+def cglow_wide_flow(glow_blob, x, y, K=1, L=1, learn_top=False, widths=(8, 16, 8), y_bins=256.0):
+    """cglow_levels_flow at the hidden sizes ``widths`` and any finite y_bins > 0
+    (nfdpf_cglow_wide_flow): x, y [M,3,8,8] -> (the final z, [M,24,2,2] at L = 2 and [M,12,4,4]
+    at L = 1; nll [M])."""
+    require_device(x, "cglow_wide_flow")
+    M = x.shape[0]
+    if tuple(x.shape[1:]) != (3, 8, 8) or tuple(y.shape) != tuple(x.shape):
+        raise NfdpfError(f"cglow_wide_flow: x and y must both be [M, 3, 8, 8] (192-wide encodings; got "
+                         f"{tuple(x.shape)}, {tuple(y.shape)})")
+    x, y = _c(x), _c(y)
+    glow_blob, top, (xh, xs, yh), ld0 = _wide_blob(glow_blob, K, L, learn_top, widths, y_bins, "cglow_wide_flow")
+    z = torch.empty((M, 24, 2, 2) if int(L) == 2 else (M, 12, 4, 4), device=x.device, dtype=f32)
+    nll = torch.empty((M,), device=x.device, dtype=f32)
+    if M == 0:  # (empty tensors have no pointer to pass)
+        return z, nll
+    check(lib().nfdpf_cglow_wide_flow(ptr(glow_blob), int(K), int(L), top, ptr(x), ptr(y), int(M), ptr(z), ptr(nll),
+                                      xh, xs, yh, ld0, stream_ptr(x.device)), "nfdpf_cglow_wide_flow")
     return z, nll
 
 

@@ -154,7 +154,9 @@ def cglow_levels_tensors(glow: nn.Module, get=_same):
     """CondGlowModel with K in 1..4, L in 1..2 and any learn_top, for csrc/cglow_levels.hip
     (layout: csrc/cglow_levels.hpp): the K level-1 steps as cglow_tensors; at L = 2 the Split2d
     conv tap-major and its bias, then the K level-2 steps, each as _cglow_step_tensors; with
-    learn_top the tail [new_mean | new_logs].  A pure gather, like cglow_tensors."""
+    learn_top the tail [new_mean | new_logs].  A pure gather, like cglow_tensors, and general in
+    the hidden sizes: at sizes other than 8 / 16 / 8 it is the blob of csrc/cglow_wide.hip (layout:
+    csrc/cglow_widths.hpp)."""
     K, L = glow.flow.K, glow.flow.L
     if not (1 <= K <= CGLOW_MAX_K and 1 <= L <= CGLOW_MAX_L):
         raise ValueError(f"the CGLOW levels kernel is built for flow_depth K in 1..{CGLOW_MAX_K} and num_levels L in "
