@@ -460,6 +460,13 @@ NFDPF_API int nfdpf_particle_init(const float *start_xy, int B, int N, float wid
  * probe of the bit-exact resampler's building block; no reference counterpart. */
 NFDPF_API int nfdpf_cascade_row_sum(const float *x, int B, int N, int variant, float *out, void *stream);
 
+/* The kernels' fp64 wave reduction on one 64-lane wave per row: x [B][K][64] -> out [B][K][64], every
+ * lane its wave's sum of value k (wave-uniform).  K = 1, 2 or 4 values reduced together.  Fixed
+ * order: lane pairs (xor 1), quads (xor 2), the half-row mirror, the row mirror, then the four
+ * 16-lane rows as (r0 + r1) + (r2 + r3).  A test probe of the exchanges' building block; no
+ * reference counterpart. */
+NFDPF_API int nfdpf_wave_sum_dpp(const double *x, int B, int K, double *out, void *stream);
+
 /* One iteration of the T loop of DPF.filtering_pos (DPFs.py:160-214), fused:
  * ESS gate (batch-global, read from ess_all) -> [soft resample | OT result] -> motion ->
  * nf_dyn inverse -> NF proposal -> nf_dyn forward -> densities -> measurement ->

@@ -124,6 +124,19 @@ __device__ __forceinline__ double dpp_d(double v) {
   return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
 }
 constexpr int kDppXor1 = 0xB1, kDppXor2 = 0x4E, kDppHalfMirror = 0x141, kDppMirror = 0x140;
+// dpp_d without an `old` operand: with every row and bank enabled and a lane pattern whose source
+// is always inside the row (the four above; the row broadcasts of wave_sum_rows_*, whose masked-off
+// rows are never read), `old` is never selected -- but dpp_d's, the live
+// source, costs two v_mov_b32 copies and a wait state per move (the destination is tied to it).
+// Here the two v_mov_b32_dpp read the source registers directly.  Only under a full exec mask: a
+// lane whose source lane is disabled gets an undefined value (dpp_d: its own -- what a max wants).
+template <int CTRL, int ROWMASK = 0xf>
+__device__ __forceinline__ double dpp_d_mov(double v) {
+  const long long x = __double_as_longlong(v);
+  const int lo = __builtin_amdgcn_mov_dpp((int)x, CTRL, ROWMASK, 0xf, false);
+  const int hi = __builtin_amdgcn_mov_dpp((int)(x >> 32), CTRL, ROWMASK, 0xf, false);
+  return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
+}
 
 // a double moved by DPP with 0 where the source lane is out of the row (or the row masked off)
 template <int CTRL, int ROWMASK = 0xf>
@@ -156,28 +169,51 @@ __device__ __forceinline__ double readlane_d(double v, int l) {
   return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
 }
 
+// The four row totals t0..t3 (every lane of row r holds t_r) combined as (t0 + t1) + (t2 + t3)
+// without leaving the VGPRs: row_bcast15 gives rows 1 and 3 their left neighbour's total (t1 + t0,
+// t3 + t2: IEEE addition commutes, the same bits), row_bcast31 gives row 3 row 1's pair sum.  The
+// result is in row 3 (rows 0..2 hold undefined values); wave_sum_rows_get reads it, wave-uniform.
+// (Eight v_readlane_b32 per value, four copies back to VGPRs and three adds before: 16 SGPRs
+// per two values held where the coupling nets' weights want them.)
+constexpr int kDppBcast15 = 0x142, kDppBcast31 = 0x143;
+__device__ __forceinline__ double wave_sum_rows_a(double v) { return v + dpp_d_mov<kDppBcast15, 0xa>(v); }
+__device__ __forceinline__ double wave_sum_rows_b(double v) { return v + dpp_d_mov<kDppBcast31, 0x8>(v); }
+__device__ __forceinline__ double wave_sum_rows_get(double v) { return readlane_d(v, 63); }
+
 __device__ __forceinline__ double wave_sum_dpp(double v) {
-  v += dpp_d<kDppXor1>(v);
-  v += dpp_d<kDppXor2>(v);
-  v += dpp_d<kDppHalfMirror>(v);
-  v += dpp_d<kDppMirror>(v);
-  return (readlane_d(v, 0) + readlane_d(v, 16)) + (readlane_d(v, 32) + readlane_d(v, 48));
+  v += dpp_d_mov<kDppXor1>(v);
+  v += dpp_d_mov<kDppXor2>(v);
+  v += dpp_d_mov<kDppHalfMirror>(v);
+  v += dpp_d_mov<kDppMirror>(v);
+  return wave_sum_rows_get(wave_sum_rows_b(wave_sum_rows_a(v)));
 }
 // wave_sum_dpp of K values at once, step by step across the values: the K butterfly chains
 // are independent, so their DPP / fp64-add latencies overlap (same arithmetic per value).
+// One step of it (0..3: the butterflies, 4..5: the rows' totals, 6: the result made uniform), for
+// a caller that spreads the steps through other work: the same additions in the same order.
+template <int STEP, int K>
+__device__ __forceinline__ void wave_sum_dpp_step(double (&v)[K]) {
+  static_assert(STEP >= 0 && STEP <= 6, "wave_sum_dpp_step: steps 0..6");
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    if constexpr (STEP == 0) v[k] += dpp_d_mov<kDppXor1>(v[k]);
+    if constexpr (STEP == 1) v[k] += dpp_d_mov<kDppXor2>(v[k]);
+    if constexpr (STEP == 2) v[k] += dpp_d_mov<kDppHalfMirror>(v[k]);
+    if constexpr (STEP == 3) v[k] += dpp_d_mov<kDppMirror>(v[k]);
+    if constexpr (STEP == 4) v[k] = wave_sum_rows_a(v[k]);
+    if constexpr (STEP == 5) v[k] = wave_sum_rows_b(v[k]);
+    if constexpr (STEP == 6) v[k] = wave_sum_rows_get(v[k]);
+  }
+}
 template <int K>
 __device__ __forceinline__ void wave_sum_dpp_n(double (&v)[K]) {
-#pragma unroll
-  for (int k = 0; k < K; ++k) v[k] += dpp_d<kDppXor1>(v[k]);
-#pragma unroll
-  for (int k = 0; k < K; ++k) v[k] += dpp_d<kDppXor2>(v[k]);
-#pragma unroll
-  for (int k = 0; k < K; ++k) v[k] += dpp_d<kDppHalfMirror>(v[k]);
-#pragma unroll
-  for (int k = 0; k < K; ++k) v[k] += dpp_d<kDppMirror>(v[k]);
-#pragma unroll
-  for (int k = 0; k < K; ++k)
-    v[k] = (readlane_d(v[k], 0) + readlane_d(v[k], 16)) + (readlane_d(v[k], 32) + readlane_d(v[k], 48));
+  wave_sum_dpp_step<0>(v);
+  wave_sum_dpp_step<1>(v);
+  wave_sum_dpp_step<2>(v);
+  wave_sum_dpp_step<3>(v);
+  wave_sum_dpp_step<4>(v);
+  wave_sum_dpp_step<5>(v);
+  wave_sum_dpp_step<6>(v);
 }
 __device__ __forceinline__ float wave_max_dpp(float v) {
   v = fmaxf(v, dpp_f<kDppXor1>(v));

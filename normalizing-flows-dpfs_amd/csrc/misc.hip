@@ -41,9 +41,38 @@ __global__ __launch_bounds__(64) void cascade_row_sum_kernel(const float *__rest
   if (threadIdx.x == 0) out[blockIdx.x] = s;
 }
 
+// The wave reductions of common.hpp on one wave per row: K = 1 wave_sum_dpp, K = 2 / 4
+// wave_sum_dpp_n<K> of x[row][k][lane]; every lane writes what it got (the result is wave-uniform)
+template <int K>
+__global__ __launch_bounds__(64) void wave_sum_dpp_kernel(const double *__restrict__ x, double *__restrict__ out) {
+  const int64_t o = (int64_t)blockIdx.x * K * 64 + threadIdx.x;
+  double v[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) v[k] = x[o + 64 * k];
+  if constexpr (K == 1)
+    v[0] = wave_sum_dpp(v[0]);
+  else
+    wave_sum_dpp_n(v);
+#pragma unroll
+  for (int k = 0; k < K; ++k) out[o + 64 * k] = v[k];
+}
+
 }  // namespace nfdpf
 
 using namespace nfdpf;
+
+extern "C" int nfdpf_wave_sum_dpp(const double *x, int B, int K, double *out, void *stream) {
+  NFDPF_REQUIRE(x && out && B >= 0, "nfdpf_wave_sum_dpp: bad arguments");
+  NFDPF_REQUIRE(K == 1 || K == 2 || K == 4, "nfdpf_wave_sum_dpp: K must be 1, 2 or 4");
+  if (B == 0) return NFDPF_OK;
+  if (K == 1)
+    wave_sum_dpp_kernel<1><<<B, 64, 0, as_stream(stream)>>>(x, out);
+  else if (K == 2)
+    wave_sum_dpp_kernel<2><<<B, 64, 0, as_stream(stream)>>>(x, out);
+  else
+    wave_sum_dpp_kernel<4><<<B, 64, 0, as_stream(stream)>>>(x, out);
+  return launch_status("nfdpf_wave_sum_dpp");
+}
 
 extern "C" int nfdpf_cascade_row_sum(const float *x, int B, int N, int variant, float *out, void *stream) {
   NFDPF_REQUIRE(x && out && B >= 0 && N >= 1, "nfdpf_cascade_row_sum: bad arguments");

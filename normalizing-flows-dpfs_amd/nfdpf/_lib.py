@@ -151,6 +151,7 @@ SIGNATURES = {
     "nfdpf_particle_init": (c_int, [c_void_p, c_int, c_int, c_float, c_int, c_uint64, c_int64, c_void_p, c_void_p,
                                     c_void_p]),
     "nfdpf_cascade_row_sum": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "nfdpf_wave_sum_dpp": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "nfdpf_filter_step": (c_int, [POINTER(FilterDesc), c_void_p]),
     "nfdpf_filter_tiled_workspace_bytes": (c_int64, [c_int, c_int, c_int]),
     "nfdpf_filter_tiled_tiles": (c_int, [c_int]),
