@@ -683,6 +683,34 @@ NFDPF_API int nfdpf_pass_verify(const double *parts, const float *lw_sum, int T,
 NFDPF_API int nfdpf_ess_row_terms(const double *parts, int T, int B, int N, int t0, float *terms, void *stream);
 NFDPF_API int nfdpf_ess_gate_terms(const float *terms, int T, int B, int N, int force, int32_t *gates, void *stream);
 
+/* The frame encoder in eval mode (model/models.py:10-60, the encoder call of DPFs.py:177):
+ * 5 x [Conv2d(4, stride 2, pad 1, no bias) -> ReLU -> BatchNorm2d with its running statistics]
+ * over channels 3 16 32 64 128 256, Flatten, Linear(4096, H) -- six implicit GEMMs on
+ * v_mfma_f32_16x16x4_f32, fp32 throughout, one launch per layer per chunk of 256 frames
+ * (csrc/frame_enc.hip; layout, fragment maps and the chain order: csrc/frame_enc.hpp).
+ *   params: nfdpf_frame_encoder_params_size(H) floats, 16-byte aligned (packed by
+ *     nfdpf.pack.frame_encoder_tensors): per conv layer the weights in B-fragment order, then the
+ *     BatchNorm as a per-channel (a, b) with y = a relu(conv) + b; then the Linear's weights in
+ *     the same order (columns permuted to the channels-last flatten) and its bias.
+ *     H: 16, 32, 64 or 192; the size query returns -1 for any other width.
+ *   frames: [B][T][3][128][128]; frame (b, t) at frames + b b_stride + t t_stride (floats), its
+ *     3 x 128 x 128 image contiguous -- obs[:, :T] of a longer tensor is read in place.
+ *   out: [B][T][H]; encoding (b, t) at out + b out_b_stride + t out_t_stride.
+ *   layers (nullable; for tests, small calls): the five post-BatchNorm activations of all B T
+ *     frames in NCHW order, one layer after another: [B T][16][64][64], [B T][32][32][32],
+ *     [B T][64][16][16], [B T][128][8][8], [B T][256][4][4] (126976 floats per frame).
+ *   workspace: nfdpf_frame_encoder_workspace_bytes(B T) bytes, 16-byte aligned: the activations
+ *     of one chunk of min(B T, 256) frames (-1 for a negative count).
+ * Every output element is one fmaf chain in an order fixed by its own indices: a frame's
+ * encoding does not depend on the other frames of the call, on B, T or the chunk it lands in.
+ * An H not built, a negative size or stride, a NULL params / frames / out / workspace:
+ * NFDPF_EINVAL with a message, nothing launched.  B T == 0: OK, nothing launched. */
+NFDPF_API int64_t nfdpf_frame_encoder_params_size(int H);
+NFDPF_API int64_t nfdpf_frame_encoder_workspace_bytes(int64_t frames);
+NFDPF_API int nfdpf_frame_encoder(const float *params, int H, const float *frames, int B, int T, int64_t b_stride,
+                                  int64_t t_stride, float *out, int64_t out_b_stride, int64_t out_t_stride,
+                                  float *layers, void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,13 +28,22 @@ from model.models import (build_conditional_glow, build_conditional_nf, build_de
                           proposal_likelihood)
 from nfdpf._lib import (NfdpfError, cglow_widths_supported, meas_width_supported, require_cglow_widths,
                         require_meas_width)
+from nfdpf import ops as _ops
 from nfdpf.engine import FilterConfig, FilterEngine, ShardInfo
 from nfdpf.gradsync import GradBucket, global_mean, sharded_supervised_loss, world_size
+from nfdpf.pack import blob, frame_encoder_sources, frame_encoder_tensors
 from resamplers.resamplers import resampler
 from utils import (checkpoint_state, compute_normal_density, load_model, normalize_log_probs,
                    particle_initialization)
 
 device = torch.device("cuda") if torch.cuda.is_available() else torch.device("cpu")
+
+
+
+def hip_encoder_enabled():
+    """NFDPF_HIP_ENCODER=0 keeps the frame encoder of the no-grad filtering path on PyTorch/MIOpen
+    (the T-call loop), for comparison; read at each call."""
+    return os.environ.get("NFDPF_HIP_ENCODER", "1") != "0"
 
 
 class _NullLogger:
@@ -169,6 +178,12 @@ class DPF(nn.Module):
     def _frame_encodings(self, obs, T):
         if isinstance(self.encoder, nn.Identity):
             return obs[:, :T].float()
+        if hip_encoder_enabled() and _ops.frame_encoder_supported(self.encoder, obs):
+            # the real conv stack in eval mode, from raw frames: csrc/frame_enc.hip, no MIOpen call
+            enc = self.encoder
+            eblob = blob(self, "frame_encoder", frame_encoder_sources(enc), lambda: frame_encoder_tensors(enc),
+                         obs.device)
+            return _ops.frame_encoder(eblob, obs[:, :T], enc[-1].out_features)
         return torch.stack([self.encoder(obs[:, t].float()) for t in range(T)], dim=1)
 
     def filter_config(self) -> FilterConfig:

@@ -4,7 +4,11 @@ measurement models with the reference's names, signatures and state_dict keys.
 Hot-path pieces run on libnfdpf: the flow stacks (via nf.models), the measurement models
 (``nfdpf_measurement``) and -- inside ``DPF.filtering_pos`` -- everything fused into one
 kernel per step (nfdpf.engine).  The frame encoder / decoder CNNs are per-image work
-(B x T frames, not B x N x T particles) and stay on PyTorch/MIOpen.
+(B x T frames, not B x N x T particles): the modules built here are plain PyTorch, and their own
+``forward`` runs on PyTorch/MIOpen (training, the decoder, the autoencoder loss).  At inference
+time ``DPF._frame_encodings`` runs the encoder's eval-mode forward from raw frames on
+csrc/frame_enc.hip instead (nfdpf.ops.frame_encoder; ``NFDPF_HIP_ENCODER=0`` keeps the loop over
+the module).
 """
 import math
 

@@ -176,6 +176,10 @@ SIGNATURES = {
     "nfdpf_ess_gate_tiled_batch": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "nfdpf_pass_verify": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                   c_void_p]),
+    "nfdpf_frame_encoder_params_size": (c_int64, [c_int]),
+    "nfdpf_frame_encoder_workspace_bytes": (c_int64, [c_int64]),
+    "nfdpf_frame_encoder": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int64, c_int64, c_void_p, c_int64,
+                                    c_int64, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

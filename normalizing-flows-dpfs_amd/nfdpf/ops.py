@@ -700,6 +700,94 @@ def cglow_levels_flow_backward(glow_blob, x, y, g_z, g_nll, K=1, L=1, learn_top=
     return gx, gy, g_glow
 
 
+FRAME_ENC_LAYER_SHAPES = ((16, 64, 64), (32, 32, 32), (64, 16, 16), (128, 8, 8), (256, 4, 4))
+
+
+def frame_encoder(blob, frames, H, keep_layers=False, out=None):
+    """The frame encoder in eval mode (model.models._conv_stack; nfdpf_frame_encoder): frames
+    [B, T, 3, 128, 128] float32 on the device (B and T may be strided: obs[:, :T] is read in
+    place), blob from nfdpf.pack.frame_encoder_tensors -> encodings [B, T, H] (written into
+    ``out`` when given: a [B, T, H] view whose last dimension is contiguous).  With keep_layers
+    also the five post-BatchNorm activations, NCHW, as a list of [B, T, C, h, w] tensors."""
+    require_device(frames, "frame_encoder")
+    if frames.dtype != f32:
+        raise NfdpfError(f"frame_encoder: frames must be float32 (got {frames.dtype})")
+    if frames.dim() != 5 or tuple(frames.shape[2:]) != (3, 128, 128):
+        raise NfdpfError(f"frame_encoder: frames must be [B, T, 3, 128, 128] (got {tuple(frames.shape)})")
+    n = int(lib().nfdpf_frame_encoder_params_size(int(H)))
+    if n < 0:
+        raise NfdpfError(f"frame_encoder: built for encoding widths 16, 32, 64 and 192 (got {H})")
+    if blob.dtype != f32 or not blob.is_cuda or int(blob.numel()) != n:
+        raise NfdpfError(f"frame_encoder: parameter blob must be {n} float32 on the device for H = {H} "
+                         f"(got {int(blob.numel())} {blob.dtype} on {blob.device})")
+    B, T = int(frames.shape[0]), int(frames.shape[1])
+    if B * T and frames.stride()[2:] != (128 * 128, 128, 1):
+        frames = frames.contiguous()
+    if out is None:
+        out = torch.empty((B, T, int(H)), device=frames.device, dtype=f32)
+    elif (tuple(out.shape) != (B, T, int(H)) or out.dtype != f32 or out.device != frames.device
+          or (B * T and out.stride(2) != 1)):
+        raise NfdpfError(f"frame_encoder: out must be a float32 [B, T, H] = {(B, T, int(H))} view on the frames' "
+                         f"device with a contiguous last dimension")
+    per = sum(c * h * w for c, h, w in FRAME_ENC_LAYER_SHAPES)
+    acts = torch.empty(B * T * per, device=frames.device, dtype=f32) if keep_layers else None
+    ws = workspace(int(lib().nfdpf_frame_encoder_workspace_bytes(B * T)), frames.device, tag="frame_enc")
+    blob = blob.contiguous()
+    check(lib().nfdpf_frame_encoder(ptr(blob), int(H), ptr(frames), B, T, frames.stride(0), frames.stride(1),
+                                    ptr(out), out.stride(0), out.stride(1), ptr(acts), _aligned_ptr(ws),
+                                    stream_ptr(frames.device)), "nfdpf_frame_encoder")
+    if not keep_layers:
+        return out
+    layers, off = [], 0
+    for c, h, w in FRAME_ENC_LAYER_SHAPES:
+        layers.append(acts[off:off + B * T * c * h * w].view(B, T, c, h, w))
+        off += B * T * c * h * w
+    return out, layers
+
+
+def frame_encoder_width(encoder):
+    """H when ``encoder`` has exactly the structure of model.models._conv_stack(H) -- five
+    [Conv2d(4, stride 2, pad 1, no bias) ReLU BatchNorm2d (affine, running statistics)] over
+    channels 3 16 32 64 128 256, Flatten, Linear(4096, H) -- with H built; else None."""
+    nn = torch.nn
+    if not isinstance(encoder, nn.Sequential) or len(encoder) != 17:
+        return None
+    chans = (3, 16, 32, 64, 128, 256)
+    for l in range(5):
+        conv, relu, bn = encoder[3 * l], encoder[3 * l + 1], encoder[3 * l + 2]
+        if not (type(conv) is nn.Conv2d and type(relu) is nn.ReLU and type(bn) is nn.BatchNorm2d):
+            return None
+        if (conv.in_channels, conv.out_channels) != (chans[l], chans[l + 1]) or conv.bias is not None:
+            return None
+        if (conv.kernel_size, conv.stride, conv.padding, conv.dilation, conv.groups, conv.padding_mode) != \
+                ((4, 4), (2, 2), (1, 1), (1, 1), 1, "zeros"):
+            return None
+        if bn.num_features != chans[l + 1] or not bn.affine or not bn.track_running_stats or bn.running_mean is None:
+            return None
+    flat, lin = encoder[15], encoder[16]
+    if not (type(flat) is nn.Flatten and type(lin) is nn.Linear) or (flat.start_dim, flat.end_dim) != (1, -1):
+        return None
+    if lin.in_features != 4096 or lin.bias is None or int(lib().nfdpf_frame_encoder_params_size(lin.out_features)) < 0:
+        return None
+    if any(p.dtype != f32 for p in encoder.parameters()):
+        return None
+    return int(lin.out_features)
+
+
+def frame_encoder_supported(encoder, obs) -> bool:
+    """Can nfdpf_frame_encoder stand in for ``encoder`` on ``obs``?  Only for the exact
+    _conv_stack structure (frame_encoder_width) in eval mode, with autograd not recording, on a
+    float32 HIP tensor [B, T', 3, 128, 128]."""
+    if not (torch.is_tensor(obs) and obs.is_cuda and obs.dtype == f32 and obs.dim() == 5
+            and tuple(obs.shape[2:]) == (3, 128, 128)):
+        return False
+    if frame_encoder_width(encoder) is None or any(m.training for m in encoder.modules()):
+        return False
+    if torch.is_grad_enabled() and (obs.requires_grad or any(p.requires_grad for p in encoder.parameters())):
+        return False
+    return True
+
+
 def particle_init(start_xy, B, N, width, true_state, seed, row_base=0, device=None):
     """particle_initialization (utils.py:46-62), device RNG -> (x [B,N,2], logw [B,N])."""
     device = device if device is not None else start_xy.device

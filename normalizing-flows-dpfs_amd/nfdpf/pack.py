@@ -378,6 +378,72 @@ def crnvp_mfma_ok(encoder: nn.Module, flows) -> bool:
     return True
 
 
+FRAME_ENC_CHANNELS = (3, 16, 32, 64, 128, 256)  # csrc/frame_enc.hpp kChan
+FRAME_ENC_WIDTHS = (16, 32, 64, 192)            # the Linear widths H the library is built for
+FRAME_ENC_LIN_BN = 16                            # csrc/frame_enc.hpp kLinBN
+
+
+def frame_enc_frag(wk: torch.Tensor, bn: int) -> torch.Tensor:
+    """A GEMM weight Wk [K, N] (K a multiple of 16, N of bn, bn of 16) as the B operands of the
+    frame encoder's v_mfma_f32_16x16x4_f32 chain (csrc/frame_enc.hpp): [N / bn][K / 16 (q)]
+    [bn / 16 (nt)][lane 64][i 4] with entry Wk[16 q + 4 (lane >> 4) + i][bn nb + 16 nt + (lane & 15)]."""
+    K, N = wk.shape
+    nb, q, nt = torch.arange(N // bn), torch.arange(K // 16), torch.arange(bn // 16)
+    lane, i = torch.arange(64), torch.arange(4)
+    k = 16 * q[None, :, None, None, None] + 4 * (lane >> 4)[None, None, None, :, None] + i
+    n = bn * nb[:, None, None, None, None] + 16 * nt[None, None, :, None, None] + (lane & 15)[None, None, None, :, None]
+    return wk[k.expand(len(nb), len(q), len(nt), 64, 4), n.expand(len(nb), len(q), len(nt), 64, 4)]
+
+
+def bn_fold(bn: nn.BatchNorm2d):
+    """Eval-mode BatchNorm2d as the per-channel affine y = a x + b: a = gamma / sqrt(running_var +
+    eps), b = beta - running_mean a (float64, each rounded to float32 once)."""
+    a = bn.weight.detach().double() / torch.sqrt(bn.running_var.detach().double() + bn.eps)
+    b = bn.bias.detach().double() - bn.running_mean.detach().double() * a
+    return a.float(), b.float()
+
+
+def frame_encoder_modules(seq: nn.Module):
+    """(convs, batch norms, linear) of a model.models._conv_stack."""
+    mods = list(seq)
+    return ([m for m in mods if isinstance(m, nn.Conv2d)], [m for m in mods if isinstance(m, nn.BatchNorm2d)],
+            [m for m in mods if isinstance(m, nn.Linear)][0])
+
+
+def frame_encoder_sources(seq: nn.Module):
+    """The tensors a frame-encoder blob depends on: the parameters AND the BatchNorm running
+    statistics (buffers: a train-mode forward updates them in place, and the blob folds them).
+    num_batches_tracked is listed with them: the native batch-norm kernel writes running_mean /
+    running_var without moving their version counters, while the module bumps the step count
+    beside every such update -- that counter is what the cache sees change."""
+    _, bns, _ = frame_encoder_modules(seq)
+    out = list(seq.parameters())
+    for bn in bns:
+        out += [bn.running_mean, bn.running_var, bn.num_batches_tracked]
+    return out
+
+
+def frame_encoder_tensors(seq: nn.Module):
+    """model.models._conv_stack(H) in eval mode as the blob of csrc/frame_enc.hip (layout:
+    csrc/frame_enc.hpp): per conv layer the weight as the GEMM matrix Wk[(4 kh + kw) cin + c][n]
+    in frame_enc_frag order with column blocks of min(cout, 64), then the BatchNorm folded to
+    (a, b); then the Linear's weight with its columns permuted from Flatten's c 16 + p to the
+    channels-last 256 p + c (p = 4 h + w), in frame_enc_frag order with column blocks of 16, and
+    its bias.  Pass frame_encoder_sources(seq) as the cache key to pack.blob."""
+    convs, bns, lin = frame_encoder_modules(seq)
+    out = []
+    for conv, bn in zip(convs, bns):
+        w = conv.weight.detach()  # [cout][cin][kh][kw]
+        cout = w.shape[0]
+        wk = w.permute(2, 3, 1, 0).reshape(-1, cout)
+        out += [frame_enc_frag(wk, min(cout, 64)), *bn_fold(bn)]
+    w = lin.weight.detach()  # [H][c 16 + p]
+    H = w.shape[0]
+    wk = w.reshape(H, 256, 16).permute(2, 1, 0).reshape(4096, H)
+    out += [frame_enc_frag(wk, FRAME_ENC_LIN_BN), lin.bias.detach()]
+    return out
+
+
 class BlobCache:
     """Flat fp32 copy of a parameter set on one device in a kernel layout, rebuilt only when
     a source parameter changes (storage, version counter)."""
