@@ -741,15 +741,8 @@ extern "C" int nfdpf_cglow_measurement(const float *pe_params, const float *glow
   NFDPF_REQUIRE(K >= 1 && K <= kMaxK, "nfdpf_cglow_measurement: built for flow_depth K in 1..4 (got %d)", K);
   NFDPF_REQUIRE(B >= 0 && N >= 1, "nfdpf_cglow_measurement: bad sizes");
   if (B == 0) return NFDPF_OK;
-  const int64_t tiles = ((int64_t)B * N + kTileP - 1) / kTileP;
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) == hipSuccess) {
-    int v = 0;
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-  }
-  // a persistent grid of exactly the resident workgroups (3 per CU: LDS 50 KB, 162 VGPRs):
-  // more would start a second, late round of workgroups and leave the tail unbalanced
-  const int grid = (int)std::min<int64_t>(tiles, (int64_t)cus * kCgWgs);
+  // a persistent grid of exactly the resident workgroups (3 per CU: LDS 50 KB, 162 VGPRs)
+  const int grid = persistent_grid(((int64_t)B * N + kTileP - 1) / kTileP, kCgWgs);
   if (K == 1)
     cglow_kernel<false, false><<<grid, kThreads, 0, as_stream(stream)>>>(
         pe_params, glow_params, enc, enc_rs, x, x_rs, B, N, lik, lik_rs, nullptr, nullptr, 1.0f, 1);
@@ -759,15 +752,6 @@ extern "C" int nfdpf_cglow_measurement(const float *pe_params, const float *glow
   return launch_status("nfdpf_cglow_measurement");
 }
 
-static int cglow_grid(int64_t tiles) {
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) == hipSuccess) {
-    int v = 0;
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-  }
-  return (int)std::min<int64_t>(tiles, (int64_t)cus * kCgWgs);
-}
-
 extern "C" int nfdpf_cglow_flow(const float *glow_params, int K, const float *x, const float *y, int64_t M,
                                 float *z, float *nll, void *stream) {
   NFDPF_REQUIRE(glow_params && x && y && nll, "nfdpf_cglow_flow: null pointer");
@@ -775,7 +759,7 @@ extern "C" int nfdpf_cglow_flow(const float *glow_params, int K, const float *x,
   NFDPF_REQUIRE(M >= 0 && M <= (int64_t)INT32_MAX, "nfdpf_cglow_flow: bad size");
   if (M == 0) return NFDPF_OK;
   // B = M rows of N = 1 (y row m is sample m), the condition x given, out_sign -1: nll
-  const int grid = cglow_grid((M + kTileP - 1) / kTileP);
+  const int grid = persistent_grid((M + kTileP - 1) / kTileP, kCgWgs);
   if (K == 1)
     cglow_kernel<false, false><<<grid, kThreads, 0, as_stream(stream)>>>(glow_params, glow_params, y, kE, nullptr, 0,
                                                                          (int)M, 1, nll, 1, x, z, -1.0f, 1);
@@ -792,7 +776,7 @@ extern "C" int nfdpf_cglow_flow(const float *glow_params, int K, const float *x,
 int nfdpf::cglow_forward_mid(const float *pe, const float *glow, int nsteps, const float *enc, int64_t enc_rs,
                              const float *x, int64_t x_rs, int B, int N, const float *xin, float *zmid,
                              hipStream_t st) {
-  const int grid = cglow_grid(((int64_t)B * N + kTileP - 1) / kTileP);
+  const int grid = persistent_grid(((int64_t)B * N + kTileP - 1) / kTileP, kCgWgs);
   cglow_kernel<true, true><<<grid, kThreads, 0, st>>>(pe, glow, enc, enc_rs, x, x_rs, B, N, nullptr, 0, xin, zmid,
                                                       1.0f, nsteps);
   return launch_status("cglow_forward_mid");

@@ -39,6 +39,19 @@ constexpr int kMaxK = 4;  // flow depths the kernels take: the blob holds K step
 
 }  // namespace cg
 
+// Host: the grid of a persistent kernel that deals `tiles` tiles to its workgroups: exactly the
+// resident workgroups (CUs x wgs_per_cu; 256 CUs where the device does not say) -- more would
+// start a second, late round of workgroups and leave the tail unbalanced -- and no more than tiles.
+inline int persistent_grid(int64_t tiles, int wgs_per_cu) {
+  int dev = 0, cus = 256;
+  if (hipGetDevice(&dev) == hipSuccess) {
+    int v = 0;
+    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
+  }
+  const int64_t resident = (int64_t)cus * wgs_per_cu;
+  return (int)(tiles < resident ? tiles : resident);
+}
+
 // cglow.hip, for the K > 1 backward (cglow_bwd.hip): the first `nsteps` steps' outputs
 int cglow_forward_mid(const float *pe, const float *glow, int nsteps, const float *enc, int64_t enc_rs,
                       const float *x, int64_t x_rs, int B, int N, const float *xin, float *zmid, hipStream_t st);

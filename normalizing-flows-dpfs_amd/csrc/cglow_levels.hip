@@ -24,14 +24,15 @@
 // area `u` that holds, in turn, the encoder's hidden layers; the conditioning nets' activations;
 // the per-particle C x C 1x1-conv matrix (16 x 577 floats at C = 24; eliminated in place for its
 // log-determinant once the 1x1 conv has read it); the coupling's grids.
-#include "cglow_levels.hpp"
+//
+// The tile frame -- lane helpers, actnorm_invconv, split_squeeze, the tile's prologue and tail --
+// is cglow_tile.hpp's, shared with cglow_wide.hip; cond_nets, coupling and the MID stores are here.
+#include "cglow_tile.hpp"
 
 namespace nfdpf {
 namespace cgl {
-constexpr int kTileP = 16;
-constexpr int kThreads = 256;
+using namespace cgt;  // the tile frame: kTileP, kThreads, kWmStride, the lane helpers
 constexpr int kWgs = 2;                 // resident workgroups per CU (LDS)
-constexpr int kWmStride = kC2 * kC2 + 1;  // a particle's 1x1-conv matrix in `u`
 // the coupling's grids inside `u` (the matrix is dead by then)
 constexpr int kBufA = 0, kBufB = 3072, kFin = 5120, kUEnd = 8192;
 // the conditioning nets' activations inside `u` (dead before the last layer writes the matrix)
@@ -53,47 +54,10 @@ static_assert(sizeof(Lds) * kWgs <= 160 * 1024, "two workgroups per CU");
 typedef float f4 __attribute__((ext_vector_type(4)));
 
 static __shared__ Lds S;
-
-__device__ __forceinline__ float sigmoidf_(float v) { return 1.0f / (1.0f + expf(-v)); }
-
-// sum of buf[p * n + i], i < n, for each particle p: lane j of the particle's 16 adds i = j,
-// j + 16, ... in order, then the 16 partials meet on a DPP butterfly -- a fixed order.  Every
-// lane of the particle returns the sum.
-__device__ __forceinline__ float particle_sum(const float *buf, int n, int tid) {
-  const int p = tid >> 4, j = tid & 15;
-  float s = 0.f;
-  for (int i = j; i < n; i += 16) s += buf[p * n + i];
-  s += dpp_f<kDppXor1>(s);
-  s += dpp_f<kDppXor2>(s);
-  s += dpp_f<kDppHalfMirror>(s);
-  s += dpp_f<kDppMirror>(s);
-  return s;
-}
-
-// A wave-uniform weight pointer as a constant-address-space one in SGPRs (scalar loads); a
-// pointer argument of a non-inlined function arrives in VGPRs, hence the readfirstlane.
-__device__ __forceinline__ cfloat *uptr(const float *p) {
-  const uint64_t v = (uint64_t)p;
-  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v);
-  const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
-  return (cfloat *)(((uint64_t)hi << 32) | lo);
-}
-
-// An LDS hand-off between lanes of ONE wave (a particle's 16 lanes): a wave's LDS accesses
-// execute in order, so waiting for its own and a compiler fence suffice (as WSYNC, cglow.hip).
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_sched_barrier(0);
-}
-
-// neighbour (tap t of 3x3, pad 1) of position ps on the G x G grid, -1 outside
-template <int G>
-__device__ __forceinline__ int nbr(int ps, int t) {
-  const int rr = ps / G + t / 3 - 1, ss = ps % G + t % 3 - 1;
-  return rr >= 0 && rr < G && ss >= 0 && ss < G ? rr * G + ss : -1;
-}
+struct Tile {  // cglow_tile.hpp's view of this kernel: its S, and split_squeeze's two areas in S.u
+  static __device__ __forceinline__ Lds &lds() { return S; }
+  static constexpr int kSplitA = kBufA, kSplitB = kBufB;
+};
 
 // The two conditioning nets of a step (x_Con: three 2x2 stride-2 convs; x_Linear 8 -> 16 -> 16
 // -> OUT, tanh) -> S.an (2 C) and the C x C matrix in S.u.
@@ -204,75 +168,6 @@ __device__ __noinline__ void cond_nets(const float *__restrict__ gA, const float
         }
       }
     }
-  }
-  __syncthreads();
-}
-
-// cond-actnorm and cond-1x1 conv of S.y in place (a thread owns one (particle, position)), then
-// log|det W| by Gaussian elimination with partial pivoting in place in LDS: the particle's 16
-// lanes share the rows (rows k + j, k + j + 16 of the remaining ones in lane j); they are lanes
-// of one wave, so the elimination's hand-offs need no workgroup barrier.
-// S.ld += G G (sum logs + log|det W|).
-template <int C, int G>
-__device__ __noinline__ void actnorm_invconv(int tid) {
-  constexpr int HW = G * G;
-  if (tid < kTileP * HW) {
-    const int p = tid / HW, pos = tid % HW;
-    float y[C];
-#pragma unroll
-    for (int c = 0; c < C; ++c) y[c] = (S.y[p][c * HW + pos] + S.an[p][C + c]) * expf(S.an[p][c]);
-    const float *w = S.u + p * kWmStride;
-#pragma unroll 1
-    for (int o = 0; o < C; ++o) {
-      float acc = 0.f;
-#pragma unroll
-      for (int c = 0; c < C; ++c) acc = fmaf(w[o * C + c], y[c], acc);
-      S.y[p][o * HW + pos] = acc;
-    }
-  }
-  __syncthreads();
-  const int p = tid >> 4, j = tid & 15;
-  float *A = S.u + p * kWmStride;
-  float ldw = 0.f;
-#pragma unroll 1
-  for (int k = 0; k < C; ++k) {
-    float best = -1.f;
-    int br = k;
-    for (int r = k + j; r < C; r += 16) {
-      const float v = fabsf(A[r * C + k]);
-      if (v > best) {
-        best = v;
-        br = r;
-      }
-    }
-#pragma unroll
-    for (int m = 1; m < 16; m <<= 1) {  // (|value|, lowest row) max over the particle's lanes
-      const float ob = __shfl_xor(best, m, 16);
-      const int orow = __shfl_xor(br, m, 16);
-      if (ob > best || (ob == best && orow < br)) {
-        best = ob;
-        br = orow;
-      }
-    }
-    if (br != k)
-      for (int c = j; c < C; c += 16) {
-        const float t = A[k * C + c];
-        A[k * C + c] = A[br * C + c];
-        A[br * C + c] = t;
-      }
-    wave_sync();
-    const float piv = A[k * C + k];
-    ldw += logf(fabsf(piv));
-    for (int r = k + 1 + j; r < C; r += 16) {
-      const float f = A[r * C + k] / piv;
-      for (int c = k + 1; c < C; ++c) A[r * C + c] = fmaf(-f, A[k * C + c], A[r * C + c]);
-    }
-    wave_sync();
-  }
-  if (j == 0) {
-    float sl = 0.f;
-    for (int c = 0; c < C; ++c) sl += S.an[p][c];
-    S.ld[p] += (float)HW * sl + (float)HW * ldw;
   }
   __syncthreads();
 }
@@ -449,44 +344,8 @@ template <int C, int G>
 __device__ __forceinline__ void glow_step(const float *__restrict__ gs, int tid) {
   using St = StepL<C, G>;
   cond_nets<C>(gs + St::offA, gs + St::offI, tid);
-  actnorm_invconv<C, G>(tid);
+  actnorm_invconv<Tile, C, G>(tid);
   coupling<C, G>(gs + St::offF, tid);
-}
-
-constexpr float kLog2Pi = 1.8378770664093453f;
-
-// Split2d(12) on S.y (12 x 4 x 4): S.ld += GaussianDiag.logp(mean, logs, z2) with (mean, logs)
-// the even / odd channels of tanh(conv 6 -> 12 (3x3) of z1); then z1 squeezed to 24 x 2 x 2.
-__device__ __noinline__ void split_squeeze(const float *__restrict__ Sp, int tid) {
-  float *bufA = S.u + kBufA, *bufB = S.u + kBufB;
-  for (int i = tid; i < kTileP * 16 * kCh; i += kThreads) {
-    const int pp = i / kCh, m = i - pp * kCh, p = pp >> 4, ps = pp & 15;
-    float am = Sp[kSplitW + 2 * m], al = Sp[kSplitW + 2 * m + 1];
-#pragma unroll 1
-    for (int t = 0; t < 9; ++t) {
-      const int nb = nbr<4>(ps, t);
-      if (nb >= 0) {
-#pragma unroll
-        for (int c = 0; c < kCh; ++c) {
-          const float z1 = S.y[p][c * 16 + nb];
-          am = fmaf(Sp[(t * kCh + c) * kC + 2 * m], z1, am);
-          al = fmaf(Sp[(t * kCh + c) * kC + 2 * m + 1], z1, al);
-        }
-      }
-    }
-    const float mean = tanhf(am), logs = tanhf(al), d = S.y[p][(kCh + m) * 16 + ps] - mean;
-    bufA[i] = -0.5f * (2.0f * logs + d * d * expf(-2.0f * logs) + kLog2Pi);
-  }
-  // squeeze: channel c 4 + a 2 + b at (i, j) is z1[c][2 i + a][2 j + b]
-  for (int i = tid; i < kTileP * 96; i += kThreads) {
-    const int p = i / 96, e = i - p * 96, nc = e >> 2, np = e & 3;
-    bufB[i] = S.y[p][(nc >> 2) * 16 + (2 * (np >> 1) + ((nc >> 1) & 1)) * 4 + 2 * (np & 1) + (nc & 1)];
-  }
-  __syncthreads();
-  const float lp = particle_sum(bufA, 16 * kCh, tid);
-  if ((tid & 15) == 0) S.ld[tid >> 4] += lp;
-  for (int i = tid; i < kTileP * 96; i += kThreads) S.y[i / 96][i % 96] = bufB[i];
-  __syncthreads();
 }
 
 // the tile's state S.y (n floats per particle) to buf [M][n] (the MID forward)
@@ -517,61 +376,7 @@ __global__ __launch_bounds__(kThreads, kWgs) void cglow_levels_kernel(
   const int nz = L == 2 ? kC2 * 4 : kE;
   for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     const int64_t g0 = tile * kTileP;
-    if (tid < kTileP) {
-      const int64_t gi = g0 + tid;
-      float a = 0.f, c = 0.f;
-      int rb = 0;
-      if (gi < total) {
-        rb = (int)(gi / N);
-        if (!xin) {
-          const int i = (int)(gi - (int64_t)rb * N);
-          a = x[rb * x_rs + 2 * i];
-          c = x[rb * x_rs + 2 * i + 1];
-        }
-      }
-      S.pxy[tid][0] = a;
-      S.pxy[tid][1] = c;
-      S.row[tid] = rb;
-      S.ld[tid] = 0.f;
-    }
-    __syncthreads();
-    // y = squeeze(frame encoding of the particle's row), [c 4 + a 2 + b][4 i + j]
-    for (int i = tid; i < kTileP * kE; i += kThreads) {
-      const int p = i / kE, e = i - p * kE, ch = e >> 4, q = e & 15;
-      S.y[p][e] = enc[S.row[p] * enc_rs + (ch >> 2) * 64 + (2 * (q >> 2) + ((ch >> 1) & 1)) * 8 + 2 * (q & 3) + (ch & 1)];
-    }
-    if (xin) {
-      for (int i = tid; i < kTileP * kE; i += kThreads) {
-        const int p = i / kE, e = i - p * kE;
-        S.xs[p][e] = g0 + p < total ? xin[(g0 + p) * kE + e] : 0.f;
-      }
-    } else {
-      // particle encoder 2 -> 16 -> 32 (ReLU) -> 192 (nfdpf.pack.encoder_tensors: W1 row pairs,
-      // W2 / W3 input-major)
-      float *h1 = S.u, *h2 = S.u + kTileP * kPeH1;
-      {
-        const int p = tid >> 4, j = tid & 15;
-        const float *w1 = pe + (j >> 1) * 4 + (j & 1);
-        h1[tid] = relu(fmaf(w1[2], S.pxy[p][1], fmaf(w1[0], S.pxy[p][0], pe[kPeB1 + j])));
-      }
-      __syncthreads();
-      for (int i = tid; i < kTileP * kPeH2; i += kThreads) {
-        const int p = i >> 5, o = i & 31;
-        float acc = pe[kPeB2 + o];
-#pragma unroll
-        for (int k = 0; k < kPeH1; ++k) acc = fmaf(pe[kPeW2 + k * kPeH2 + o], h1[p * kPeH1 + k], acc);
-        h2[i] = relu(acc);
-      }
-      __syncthreads();
-      for (int i = tid; i < kTileP * kE; i += kThreads) {
-        const int p = i / kE, n = i - p * kE;
-        float acc = 0.f;
-#pragma unroll
-        for (int k = 0; k < kPeH2; ++k) acc = fmaf(pe[kPeW3 + k * kE + n], h2[p * kPeH2 + k], acc);
-        S.xs[p][n] = acc + pe[kPeW3 + kE * kPeH2 + n];
-      }
-    }
-    __syncthreads();
+    tile_load<Tile>(pe, enc, enc_rs, x, x_rs, N, xin, g0, total, tid);
 #pragma unroll 1
     for (int k = 0; k < K; ++k) {
       glow_step<kC, 4>(glow + (int64_t)k * kStep, tid);
@@ -579,7 +384,7 @@ __global__ __launch_bounds__(kThreads, kWgs) void cglow_levels_kernel(
     }
     if (L == 2) {
       const float *g2 = glow + (int64_t)K * kStep;
-      split_squeeze(g2, tid);
+      split_squeeze<Tile>(g2, tid);
       float *z2mid = MID ? zout + (int64_t)K * total * kE : nullptr;
       if constexpr (MID) mid_store(z2mid, kC2 * 4, g0, total, tid);
 #pragma unroll 1
@@ -592,35 +397,9 @@ __global__ __launch_bounds__(kThreads, kWgs) void cglow_levels_kernel(
       __syncthreads();
       continue;
     }
-    // the top Gaussian and the outputs
-    float *bufA = S.u + kBufA;
-    for (int i = tid; i < kTileP * nz; i += kThreads) {
-      const int p = i / nz, e = i - p * nz;
-      const float z = S.y[p][e], mean = top ? top[e] : 0.f, logs = top ? top[nz + e] : 0.f, d = z - mean;
-      bufA[i] = -0.5f * (2.0f * logs + d * d * expf(-2.0f * logs) + kLog2Pi);
-      if (zout && g0 + p < total) zout[(g0 + p) * nz + e] = z;
-    }
-    __syncthreads();
-    const float lp = particle_sum(bufA, nz, tid);
-    const int p = tid >> 4;
-    if ((tid & 15) == 0 && g0 + p < total) {
-      // logdet0 = -log(256) * 192, the log-dets, the top log-prob
-      const float obj = -5.545177444479562f * (float)kE + (S.ld[p] + lp);
-      const int rb = S.row[p];
-      const int i = (int)(g0 + p - (int64_t)rb * N);
-      lik[rb * lik_rs + i] = out_sign * (obj / (0.6931471805599453f * (float)kE));
-    }
-    __syncthreads();
+    // logdet0 = -log(256) * 192, a constant here
+    tile_finish<Tile>(top, nz, -5.545177444479562f * (float)kE, lik, lik_rs, zout, out_sign, N, g0, total, tid);
   }
-}
-
-static int levels_grid(int64_t tiles) {
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) == hipSuccess) {
-    int v = 0;
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-  }
-  return (int)std::min<int64_t>(tiles, (int64_t)cus * kWgs);
 }
 
 }  // namespace cgl
@@ -631,7 +410,7 @@ static int levels_grid(int64_t tiles) {
 int cglow_levels_forward_mid(const float *pe, const float *glow, int K, int L, const float *enc, int64_t enc_rs,
                              const float *x, int64_t x_rs, int B, int N, const float *xin, float *zmid,
                              hipStream_t st) {
-  const int grid = cgl::levels_grid(((int64_t)B * N + cgl::kTileP - 1) / cgl::kTileP);
+  const int grid = persistent_grid(((int64_t)B * N + cgl::kTileP - 1) / cgl::kTileP, cgl::kWgs);
   cgl::cglow_levels_kernel<true><<<grid, cgl::kThreads, 0, st>>>(pe, glow, nullptr, enc, enc_rs, x, x_rs, B, N, nullptr, 0,
                                                                 xin, zmid, 1.0f, K, L);
   return launch_status("cglow_levels_forward_mid");
@@ -656,7 +435,7 @@ extern "C" int nfdpf_cglow_levels_measurement(const float *pe_params, const floa
   NFDPF_LEVELS_RANGE("nfdpf_cglow_levels_measurement");
   NFDPF_REQUIRE(B >= 0 && N >= 1, "nfdpf_cglow_levels_measurement: bad sizes");
   if (B == 0) return NFDPF_OK;
-  const int grid = levels_grid(((int64_t)B * N + kTileP - 1) / kTileP);
+  const int grid = persistent_grid(((int64_t)B * N + kTileP - 1) / kTileP, kWgs);
   cglow_levels_kernel<false><<<grid, kThreads, 0, as_stream(stream)>>>(pe_params, glow_params, top, enc, enc_rs, x, x_rs, B, N,
                                                                  lik, lik_rs, nullptr, nullptr, 1.0f, K, L);
   return launch_status("nfdpf_cglow_levels_measurement");
@@ -669,7 +448,7 @@ extern "C" int nfdpf_cglow_levels_flow(const float *glow_params, int K, int L, c
   NFDPF_REQUIRE(M >= 0 && M <= (int64_t)INT32_MAX, "nfdpf_cglow_levels_flow: bad size");
   if (M == 0) return NFDPF_OK;
   // B = M rows of N = 1 (y row m is sample m), the condition x given, out_sign -1: nll
-  const int grid = levels_grid((M + kTileP - 1) / kTileP);
+  const int grid = persistent_grid((M + kTileP - 1) / kTileP, kWgs);
   cglow_levels_kernel<false><<<grid, kThreads, 0, as_stream(stream)>>>(glow_params, glow_params, top, y, kE, nullptr, 0, (int)M,
                                                                  1, nll, 1, x, z, -1.0f, K, L);
   return launch_status("nfdpf_cglow_levels_flow");

@@ -351,102 +351,50 @@ class measurement_model_cnf(nn.Module):
 
 
 class _CglowRunner:
-    """measurement_model_cglow's raw likelihood -nll: the fused HIP kernel forward (particle
-    encoder + CGLOW, csrc/cglow.hip) and the HIP backward (nfdpf_cglow_measurement_backward,
-    csrc/cglow_bwd.hip); ``torch`` is the PyTorch restatement (the particle encoder, then
-    CondGlowModel.torch_forward) that NFDPF_HIP_BACKWARD=0 differentiates instead, bounded to
-    RECOMPUTE_ROWS particles (nfdpf.autograd: 4 000 took 3.96 ms there, 64 000 did not finish in
-    3 minutes on the GPU box)."""
+    """measurement_model_cglow's raw likelihood -nll on the kernel ``kern`` (CondGlowModel.hip_kernel):
+    the fused HIP forward (particle encoder + CGLOW: csrc/cglow.hip, cglow_levels.hip or
+    cglow_wide.hip) and the HIP backward where the kernel has one (csrc/cglow_bwd.hip;
+    csrc/cglow_levels_bwd.hip inside the configurations it is built for; none at the sizes and
+    bins of cglow_wide.hip); ``torch`` is the PyTorch restatement (the particle encoder, then
+    CondGlowModel.torch_forward) that is differentiated elsewhere, and with NFDPF_HIP_BACKWARD=0,
+    bounded to RECOMPUTE_ROWS particles (nfdpf.autograd: 4 000 took 3.96 ms there, 64 000 did not
+    finish in 3 minutes on the GPU box)."""
 
     RECOMPUTE_ROWS = 16384
 
-    def __init__(self, model):
-        self.model = model
+    def __init__(self, model, kern):
+        self.model, self.kern = model, kern
 
     def recompute_limit(self, enc, x):
         return self.RECOMPUTE_ROWS, x.numel() // x.shape[-1]
 
-    def hip(self, enc, x):
-        from nfdpf.pack import cglow_tensors
+    def _blobs(self, device):
         m = self.model
-        pe = blob(m, "pe", m.particle_encoder, lambda: encoder_tensors(m.particle_encoder), x.device)
-        glow = blob(m, "glow", m.CGLOW, lambda: cglow_tensors(m.CGLOW), x.device)
-        return (_ops.cglow_measurement(pe, glow, enc.float(), x.float(), K=m.CGLOW.flow.K),)
+        pe = blob(m, "pe", m.particle_encoder, lambda: encoder_tensors(m.particle_encoder), device)
+        return pe, self.kern.blob(m, m.CGLOW, device)
+
+    def hip(self, enc, x):
+        pe, glow = self._blobs(x.device)
+        return (self.kern.measurement(pe, glow, enc.float(), x.float(), **self.kern.kwargs),)
 
     def torch(self, enc, x):
         return (self.model.torch_forward_raw(enc, x),)
 
     def hip_backward(self, enc, x, gouts):
-        """d/d(enc, x, encoder and CGLOW parameters) on nfdpf_cglow_measurement_backward
-        (csrc/cglow_bwd.hip); None (recompute) outside the kernel's configuration."""
-        from nfdpf.pack import blob_param_grads, cglow_tensors
-        m = self.model
-        if enc.dim() != 2 or enc.shape[-1] != 192 or x.dim() != 3 or x.shape[-1] != 2 \
-                or not m.CGLOW.kernel_supported():
+        """d/d(enc, x, encoder and CGLOW parameters) on the kernel's measurement backward; None
+        (recompute) where it has none or outside the shapes it takes."""
+        from nfdpf.pack import blob_param_grads
+        m, k = self.model, self.kern
+        if k.measurement_backward is None or enc.dim() != 2 or enc.shape[-1] != 192 or x.dim() != 3 \
+                or x.shape[-1] != 2:
             return None
-        pe = blob(m, "pe", m.particle_encoder, lambda: encoder_tensors(m.particle_encoder), x.device)
-        glow = blob(m, "glow", m.CGLOW, lambda: cglow_tensors(m.CGLOW), x.device)
+        pe, glow = self._blobs(x.device)
         g = gouts[0] if gouts[0] is not None else torch.zeros(x.shape[:2], device=x.device)
-        g_enc, gx, g_glow, g_pe = _ops.cglow_measurement_backward(pe, glow, enc.float(), x.float(), g.float(),
-                                                                  K=m.CGLOW.flow.K)
-        pe_params, gl_params = list(m.particle_encoder.parameters()), list(m.CGLOW.parameters())
-        res = blob_param_grads(m, "pe_grad", pe_params, lambda get: encoder_tensors(m.particle_encoder, get), g_pe)
-        res += blob_param_grads(m, "glow_grad", gl_params, lambda get: cglow_tensors(m.CGLOW, get), g_glow)
+        g_enc, gx, g_glow, g_pe = k.measurement_backward(pe, glow, enc.float(), x.float(), g.float(), **k.kwargs)
+        res = blob_param_grads(m, "pe_grad", list(m.particle_encoder.parameters()),
+                               lambda get: encoder_tensors(m.particle_encoder, get), g_pe)
+        res += k.param_grads(m, m.CGLOW, g_glow)
         return (g_enc.to(enc.dtype), gx.to(x.dtype)), res
-
-
-class _CglowLevelsRunner(_CglowRunner):
-    """_CglowRunner for the configurations its kernel does not take (L = 2 and / or learn_top):
-    the levels kernel forward (csrc/cglow_levels.hip) and the HIP backward of
-    csrc/cglow_levels_bwd.hip (nfdpf_cglow_levels_measurement_backward); NFDPF_HIP_BACKWARD=0
-    keeps the bounded PyTorch recompute of torch_forward_raw, for comparison."""
-
-    def hip(self, enc, x):
-        from nfdpf.pack import cglow_levels_tensors
-        m = self.model
-        g = m.CGLOW
-        pe = blob(m, "pe", m.particle_encoder, lambda: encoder_tensors(m.particle_encoder), x.device)
-        glow = blob(m, "glow_levels", g, lambda: cglow_levels_tensors(g), x.device)
-        return (_ops.cglow_levels_measurement(pe, glow, enc.float(), x.float(), K=g.flow.K, L=g.flow.L,
-                                              learn_top=g.learn_top),)
-
-    def hip_backward(self, enc, x, gouts):
-        """d/d(enc, x, encoder and CGLOW parameters) on nfdpf_cglow_levels_measurement_backward;
-        None (recompute) outside the configurations csrc/cglow_levels_bwd.hip is built for."""
-        from nfdpf.pack import blob_param_grads, cglow_levels_tensors
-        m = self.model
-        g = m.CGLOW
-        K, L = g.flow.K, g.flow.L
-        if enc.dim() != 2 or enc.shape[-1] != 192 or x.dim() != 3 or x.shape[-1] != 2 \
-                or not g.levels_kernel_supported() or not _ops.cglow_levels_backward_supported(K, L):
-            return None
-        pe = blob(m, "pe", m.particle_encoder, lambda: encoder_tensors(m.particle_encoder), x.device)
-        glow = blob(m, "glow_levels", g, lambda: cglow_levels_tensors(g), x.device)
-        gl = gouts[0] if gouts[0] is not None else torch.zeros(x.shape[:2], device=x.device)
-        g_enc, gx, g_glow, g_pe = _ops.cglow_levels_measurement_backward(pe, glow, enc.float(), x.float(), gl.float(),
-                                                                         K=K, L=L, learn_top=g.learn_top)
-        pe_params, gl_params = list(m.particle_encoder.parameters()), list(g.parameters())
-        res = blob_param_grads(m, "pe_grad", pe_params, lambda get: encoder_tensors(m.particle_encoder, get), g_pe)
-        res += blob_param_grads(m, "glow_levels_grad", gl_params, lambda get: cglow_levels_tensors(g, get), g_glow)
-        return (g_enc.to(enc.dtype), gx.to(x.dtype)), res
-
-
-class _CglowWideRunner(_CglowRunner):
-    """_CglowRunner at the hidden sizes of csrc/cglow_widths.hpp other than 8 / 16 / 8 and at bin
-    counts other than 256: the width-general forward kernel (csrc/cglow_wide.hip).  No HIP backward
-    at these sizes: the bounded PyTorch recompute of torch_forward_raw gives the gradients."""
-
-    def hip(self, enc, x):
-        from nfdpf.pack import cglow_levels_tensors
-        m = self.model
-        g = m.CGLOW
-        pe = blob(m, "pe", m.particle_encoder, lambda: encoder_tensors(m.particle_encoder), x.device)
-        glow = blob(m, "glow_levels", g, lambda: cglow_levels_tensors(g), x.device)
-        return (_ops.cglow_wide_measurement(pe, glow, enc.float(), x.float(), K=g.flow.K, L=g.flow.L,
-                                            learn_top=g.learn_top, widths=g.hidden_sizes(), y_bins=g.n_bins),)
-
-    def hip_backward(self, enc, x, gouts):
-        return None
 
 
 class measurement_model_cglow(nn.Module):
@@ -462,18 +410,12 @@ class measurement_model_cglow(nn.Module):
         with its 12x12 log-determinant, affine coupling, Gaussian log-prob), then the row-max
         shift.  Under autograd the particle encoder and every CGLOW parameter get their
         gradients through the recompute backward of _CglowRunner."""
-        if self.CGLOW.kernel_supported():
-            runner = _CglowRunner(self)
-        elif self.CGLOW.levels_kernel_supported():
-            # L = 2 and / or learn_top: csrc/cglow_levels.hip, gradients on csrc/cglow_levels_bwd.hip
-            runner = _CglowLevelsRunner(self)
-        elif self.CGLOW.wide_kernel_supported():
-            # other hidden sizes or bins: csrc/cglow_wide.hip, gradients by the PyTorch recompute
-            runner = _CglowWideRunner(self)
-        else:
+        kern = self.CGLOW.hip_kernel()
+        if kern is None:
             raise NfdpfError("measurement_model_cglow: the HIP kernels are built for the reference's CGLOW with "
                              "flow_depth K in 1..4, num_levels L in 1..2, 3x8x8 inputs, x_hidden_channels in {8, 16}, "
                              "x_hidden_size in {16, 32}, y_hidden_channels in {8, 16, 32} and finite y_bins > 0")
+        runner = _CglowRunner(self, kern)
         lik = _ag.apply(runner, (encodings, update_particles), list(self.parameters()))[0]
         return lik - lik.max(dim=-1, keepdim=True)[0]
 

@@ -16,6 +16,8 @@ sizes and bins of csrc/cglow_wide.hip it is the PyTorch recompute below.  With
 NFDPF_HIP_BACKWARD=0 it differentiates ``torch_forward`` instead, a PyTorch restatement of the
 same math run on the saved inputs (nfdpf.autograd; the forward value is the kernel's).
 ``reverse=True`` (sampling; the DPF never calls it) runs the layers' PyTorch reverse."""
+from typing import Callable, NamedTuple, Optional
+
 import numpy as np
 import torch
 import torch.nn as nn
@@ -82,94 +84,61 @@ class CondGlow(nn.Module):
         return y, logdet
 
 
-def _hidden_sizes(flow):
-    """(x_hidden_channels, x_hidden_size, y_hidden_channels) of a CondGlow's first step."""
-    st = next(l for l in flow.layers if isinstance(l, CondGlowStep))
-    lin = [m for m in st.actnorm.x_Linear if isinstance(m, nn.Linear)]
-    return lin[0].in_features, lin[0].out_features, st.affine.f[0].out_channels
+class HipKernel(NamedTuple):
+    """What CondGlowModel.hip_kernel() answers: the HIP kernel that takes the model, and what a
+    caller needs to use it.  ``kwargs`` go to every op; the backward ops are None where the
+    kernel has no HIP backward."""
+    name: str                      # "cglow" | "levels" | "wide": csrc/cglow.hip, cglow_levels.hip, cglow_wide.hip
+    blob_key: str                  # the nfdpf.pack.blob cache key of the packed parameters
+    pack: Callable                 # nfdpf.pack.cglow_tensors | cglow_levels_tensors
+    measurement: Callable          # nfdpf.ops.cglow*_measurement
+    flow: Callable                 # nfdpf.ops.cglow*_flow
+    kwargs: dict                   # K; and L, learn_top; and widths, y_bins -- as the kernel takes them
+    measurement_backward: Optional[Callable] = None
+    flow_backward: Optional[Callable] = None
+
+    def blob(self, owner, model, device):
+        """The model's packed parameters on ``device``, cached on ``owner`` under blob_key."""
+        from nfdpf.pack import blob
+        return blob(owner, self.blob_key, model, lambda: self.pack(model), device)
+
+    def param_grads(self, owner, model, g_blob):
+        """The blob-layout gradient g_blob as the model's parameter gradients."""
+        from nfdpf.pack import blob_param_grads
+        return blob_param_grads(owner, self.blob_key + "_grad", list(model.parameters()),
+                                lambda get: self.pack(model, get), g_blob)
 
 
 class _FlowRunner:
-    """nfdpf.autograd runner: the HIP kernel forward, the PyTorch restatement for backward."""
+    """nfdpf.autograd runner of CondGlowModel.forward on the kernel ``kern`` (a HipKernel): the
+    HIP forward; the HIP backward where the kernel has one (csrc/cglow_bwd.hip, or
+    csrc/cglow_levels_bwd.hip inside the configurations it is built for); else, and with
+    NFDPF_HIP_BACKWARD=0, the PyTorch recompute of torch_forward, which is general in L,
+    learn_top, the sizes and y_bins.  The wide kernel's recompute is bounded to RECOMPUTE_ROWS
+    samples like the measurement form's (model.models._CglowRunner)."""
 
-    def __init__(self, model):
-        self.model = model
+    RECOMPUTE_ROWS = 16384
+
+    def __init__(self, model, kern):
+        self.model, self.kern = model, kern
+        # (nfdpf.autograd reads the attribute: None is "unbounded")
+        self.recompute_limit = (lambda x, y: (self.RECOMPUTE_ROWS, x.shape[0])) if kern.name == "wide" else None
 
     def hip(self, x, y):
-        from nfdpf import ops
-        from nfdpf.pack import blob, cglow_tensors
-        m = self.model
-        glow = blob(m, "glow", m, lambda: cglow_tensors(m), x.device)
-        return ops.cglow_flow(glow, x, y, K=m.flow.K)
+        m, k = self.model, self.kern
+        return k.flow(k.blob(m, m, x.device), x, y, **k.kwargs)
 
     def torch(self, x, y):
         return self.model.torch_forward(x, y)
 
     def hip_backward(self, x, y, gouts):
-        """d/d(x, y, parameters) on nfdpf_cglow_flow_backward (csrc/cglow_bwd.hip)."""
-        from nfdpf import ops
-        from nfdpf.pack import blob, blob_param_grads, cglow_tensors
-        m = self.model
-        glow = blob(m, "glow", m, lambda: cglow_tensors(m), x.device)
-        g_z, g_nll = gouts
-        gx, gy, g_glow = ops.cglow_flow_backward(glow, x, y, g_z, g_nll, K=m.flow.K)
-        res = blob_param_grads(m, "glow_grad", list(m.parameters()), lambda get: cglow_tensors(m, get), g_glow)
-        return (gx, gy), res
-
-
-class _LevelsFlowRunner(_FlowRunner):
-    """The runner of the configurations _FlowRunner's kernel does not take (L = 2 and / or
-    learn_top): the levels kernel forward (csrc/cglow_levels.hip) and the HIP backward of
-    csrc/cglow_levels_bwd.hip; NFDPF_HIP_BACKWARD=0 differentiates torch_forward, which is
-    general in L and learn_top, instead."""
-
-    def hip(self, x, y):
-        from nfdpf import ops
-        from nfdpf.pack import blob, cglow_levels_tensors
-        m = self.model
-        glow = blob(m, "glow_levels", m, lambda: cglow_levels_tensors(m), x.device)
-        return ops.cglow_levels_flow(glow, x, y, K=m.flow.K, L=m.flow.L, learn_top=m.learn_top)
-
-    def hip_backward(self, x, y, gouts):
-        """d/d(x, y, parameters) on nfdpf_cglow_levels_flow_backward (csrc/cglow_levels_bwd.hip);
-        None (recompute) outside the configurations that kernel is built for."""
-        from nfdpf import ops
-        from nfdpf.pack import blob, blob_param_grads, cglow_levels_tensors
-        m = self.model
-        K, L = m.flow.K, m.flow.L
-        if not m.levels_kernel_supported() or not ops.cglow_levels_backward_supported(K, L) \
-                or tuple(x.shape[1:]) != (3, 8, 8) or tuple(y.shape) != tuple(x.shape):
+        """d/d(x, y, parameters) on the kernel's flow backward; None (recompute) where it has none."""
+        m, k = self.model, self.kern
+        if k.flow_backward is None or tuple(x.shape[1:]) != (3, 8, 8) or tuple(y.shape) != tuple(x.shape):
             return None
-        glow = blob(m, "glow_levels", m, lambda: cglow_levels_tensors(m), x.device)
         g_z, g_nll = gouts
-        gx, gy, g_glow = ops.cglow_levels_flow_backward(glow, x, y, g_z, g_nll, K=K, L=L, learn_top=m.learn_top)
-        res = blob_param_grads(m, "glow_levels_grad", list(m.parameters()), lambda get: cglow_levels_tensors(m, get),
-                               g_glow)
-        return (gx, gy), res
-
-
-class _WideFlowRunner(_FlowRunner):
-    """The runner of the hidden sizes of csrc/cglow_widths.hpp other than 8 / 16 / 8, and of bin
-    counts other than 256: the width-general forward kernel (csrc/cglow_wide.hip).  There is no
-    HIP backward at these sizes: gradients come from the PyTorch recompute of torch_forward,
-    which is general in the sizes and in y_bins, bounded to RECOMPUTE_ROWS samples like the
-    measurement form's (model.models._CglowRunner)."""
-
-    RECOMPUTE_ROWS = 16384
-
-    def recompute_limit(self, x, y):
-        return self.RECOMPUTE_ROWS, x.shape[0]
-
-    def hip(self, x, y):
-        from nfdpf import ops
-        from nfdpf.pack import blob, cglow_levels_tensors
-        m = self.model
-        glow = blob(m, "glow_levels", m, lambda: cglow_levels_tensors(m), x.device)
-        return ops.cglow_wide_flow(glow, x, y, K=m.flow.K, L=m.flow.L, learn_top=m.learn_top,
-                                   widths=m.hidden_sizes(), y_bins=m.n_bins)
-
-    def hip_backward(self, x, y, gouts):
-        return None
+        gx, gy, g_glow = k.flow_backward(k.blob(m, m, x.device), x, y, g_z, g_nll, **k.kwargs)
+        return (gx, gy), k.param_grads(m, m, g_glow)
 
 
 class CondGlowModel(nn.Module):
@@ -191,36 +160,58 @@ class CondGlowModel(nn.Module):
         return torch.zeros_like(self.new_mean), torch.zeros_like(self.new_mean)
 
     def hidden_sizes(self):
-        """(x_hidden_channels, x_hidden_size, y_hidden_channels) the model was built with."""
-        return _hidden_sizes(self.flow)
+        """(x_hidden_channels, x_hidden_size, y_hidden_channels) the model was built with (its first step's)."""
+        st = next(l for l in self.flow.layers if isinstance(l, CondGlowStep))
+        lin = [m for m in st.actnorm.x_Linear if isinstance(m, nn.Linear)]
+        return lin[0].in_features, lin[0].out_features, st.affine.f[0].out_channels
+
+    def hip_kernel(self) -> Optional[HipKernel]:
+        """THE kernel choice: the HIP kernel that takes this model, or None.  x and y are 3x8x8 and
+        K is in 1..4 for all three; then
+        cglow   csrc/cglow.hip: the reference's defaults (arguments.py:61-70): L = 1, learn_top
+                off, 256 bins, hidden 8 / 16 / 8;
+        levels  csrc/cglow_levels.hip: L in 1..2, any learn_top, 256 bins, hidden 8 / 16 / 8;
+        wide    csrc/cglow_wide.hip: L in 1..2, any learn_top, hidden sizes in the set of
+                csrc/cglow_widths.hpp (every combination of x_hidden_channels in {8, 16},
+                x_hidden_size in {16, 32}, y_hidden_channels in {8, 16, 32}), any finite y_bins > 0.
+        x_bins is not read, as in the reference."""
+        from nfdpf import ops
+        from nfdpf._lib import cglow_widths_supported
+        from nfdpf.pack import cglow_levels_tensors, cglow_tensors
+        f = self.flow
+        if not (1 <= f.K <= 4 and 1 <= f.L <= 2
+                and list(f.output_shapes[-1][1:]) == ([12, 4, 4] if f.L == 1 else [24, 2, 2])):
+            return None
+        nb, widths = float(self.n_bins), self.hidden_sizes()
+        levels = dict(K=f.K, L=f.L, learn_top=self.learn_top)
+        if nb == 256.0 and widths == (8, 16, 8):
+            if f.L == 1 and not self.learn_top:
+                return HipKernel("cglow", "glow", cglow_tensors, ops.cglow_measurement, ops.cglow_flow, dict(K=f.K),
+                                 ops.cglow_measurement_backward, ops.cglow_flow_backward)
+            bwd = ops.cglow_levels_backward_supported(f.K, f.L)  # (what csrc/cglow_levels_bwd.hip is built for)
+            return HipKernel("levels", "glow_levels", cglow_levels_tensors, ops.cglow_levels_measurement,
+                             ops.cglow_levels_flow, levels, ops.cglow_levels_measurement_backward if bwd else None,
+                             ops.cglow_levels_flow_backward if bwd else None)
+        if np.isfinite(nb) and nb > 0 and cglow_widths_supported(*widths):
+            return HipKernel("wide", "glow_levels", cglow_levels_tensors, ops.cglow_wide_measurement,
+                             ops.cglow_wide_flow, dict(levels, widths=widths, y_bins=self.n_bins))
+        return None
 
     def kernel_supported(self) -> bool:
-        """The configuration csrc/cglow.hip is built for: the reference's defaults
-        (arguments.py:61-70) with flow_depth K in 1..4: L = 1, 3x8x8 x and y, hidden 8 / 16 / 8,
-        learn_top off."""
-        f = self.flow
-        return (1 <= f.K <= 4 and f.L == 1 and not self.learn_top and float(self.n_bins) == 256.0
-                and list(f.output_shapes[-1][1:]) == [12, 4, 4] and _hidden_sizes(f) == (8, 16, 8))
+        """The configuration csrc/cglow.hip is built for (hip_kernel: cglow)."""
+        k = self.hip_kernel()
+        return k is not None and k.name == "cglow"
 
     def levels_kernel_supported(self) -> bool:
-        """The configurations csrc/cglow_levels.hip is built for: K in 1..4, L in 1..2, any
-        learn_top, 256 bins, 3x8x8 x and y, hidden 8 / 16 / 8."""
-        f = self.flow
-        return (1 <= f.K <= 4 and 1 <= f.L <= 2 and float(self.n_bins) == 256.0
-                and list(f.output_shapes[-1][1:]) == ([12, 4, 4] if f.L == 1 else [24, 2, 2])
-                and _hidden_sizes(f) == (8, 16, 8))
+        """The configurations csrc/cglow_levels.hip is built for (hip_kernel: levels, and cglow's,
+        which it takes as well)."""
+        k = self.hip_kernel()
+        return k is not None and k.name in ("cglow", "levels")
 
     def wide_kernel_supported(self) -> bool:
-        """The configurations csrc/cglow_wide.hip is built for: K in 1..4, L in 1..2, any
-        learn_top, 3x8x8 x and y, hidden sizes in the set of csrc/cglow_widths.hpp (every
-        combination of x_hidden_channels in {8, 16}, x_hidden_size in {16, 32}, y_hidden_channels
-        in {8, 16, 32}), any finite y_bins > 0.  x_bins is not read, as in the reference."""
-        from nfdpf._lib import cglow_widths_supported
-        f = self.flow
-        nb = float(self.n_bins)
-        return (1 <= f.K <= 4 and 1 <= f.L <= 2 and np.isfinite(nb) and nb > 0
-                and list(f.output_shapes[-1][1:]) == ([12, 4, 4] if f.L == 1 else [24, 2, 2])
-                and cglow_widths_supported(*_hidden_sizes(f)))
+        """The configurations csrc/cglow_wide.hip is built for: every one that has a kernel (the
+        default sizes at 256 bins are in its set; cglow.hip / cglow_levels.hip run them)."""
+        return self.hip_kernel() is not None
 
     def forward(self, x=0.0, y=None, eps_std=1.0, reverse=False):
         """reverse=False: (z, nll) of y given the condition x (CGlowModel.py:167-176), on the
@@ -235,16 +226,12 @@ class CondGlowModel(nn.Module):
                 if y is None:
                     y = modules.GaussianDiag.batchsample(x.size(0), mean, logs, eps_std)
                 return self.flow(x, y, eps_std=eps_std, reverse=True)
-        if self.kernel_supported():
-            runner = _FlowRunner(self)
-        elif self.levels_kernel_supported():
-            runner = _LevelsFlowRunner(self)
-        elif self.wide_kernel_supported():
-            runner = _WideFlowRunner(self)
-        else:
+        kern = self.hip_kernel()
+        if kern is None:
             raise NfdpfError("CondGlowModel.forward: the HIP kernels are built for K in 1..4, L in 1..2, 3x8x8 "
                              "inputs, x_hidden_channels in {8, 16}, x_hidden_size in {16, 32}, y_hidden_channels "
                              "in {8, 16, 32} and finite y_bins > 0")
+        runner = _FlowRunner(self, kern)
         z, nll = _ag.apply(runner, (x.float().contiguous(), y.float().contiguous()), list(self.parameters()))
         return z, nll
 

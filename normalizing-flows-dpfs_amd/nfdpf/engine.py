@@ -32,8 +32,8 @@ import torch.distributed as dist
 
 from . import _lib as L
 from . import ops
-from .pack import (blob, cglow_levels_tensors, cglow_tensors, encoder_tensors, filter_flow_tensors, flows_tensors,
-                   paired_mlp_tensors, pass_flow_tensors, splittable)
+from .pack import (blob, encoder_tensors, filter_flow_tensors, flows_tensors, paired_mlp_tensors, pass_flow_tensors,
+                   splittable)
 
 
 @dataclass
@@ -491,16 +491,13 @@ class FilterEngine:
         elif c.measurement == "NN":
             meas = blob(m, "meas", m.likelihood_est, lambda: paired_mlp_tensors(m.likelihood_est), dev)
         elif c.measurement == "CGLOW":
-            g = m.cglow_measurement
-            if g.kernel_supported():
-                meas = blob(m, "glow", g, lambda: cglow_tensors(g), dev)
-            elif g.levels_kernel_supported() or g.wide_kernel_supported():
-                # L = 2 and / or learn_top: the levels kernel's layout (csrc/cglow_levels.hpp); other
-                # hidden sizes or bins: the same layout at those sizes (csrc/cglow_widths.hpp)
-                meas = blob(m, "glow_levels", g, lambda: cglow_levels_tensors(g), dev)
-            else:
+            kern = m.cglow_measurement.hip_kernel()
+            if kern is None:
                 raise L.NfdpfError("FilterEngine: this CGLOW configuration has no HIP kernel (K in 1..4, L in 1..2, "
                                    "hidden sizes of csrc/cglow_widths.hpp, finite y_bins > 0)")
+            # cglow.hip's layout, or the levels kernel's (csrc/cglow_levels.hpp; at other hidden sizes
+            # csrc/cglow_widths.hpp), as the kernel that takes the model reads it
+            meas = kern.blob(m, m.cglow_measurement, dev)
         return dyn, cond, pe, meas
 
     # -- main loop --------------------------------------------------------------------------
@@ -543,12 +540,6 @@ class FilterEngine:
         if wide:
             L.require_meas_width(c.measurement, E, "FilterEngine.run")
         external = self._external = c.measurement == "CGLOW" or wide
-        # CGLOW's kernel by configuration: cglow.hip, else cglow_levels.hip, else cglow_wide.hip
-        glow_levels = glow_wide = False
-        if c.measurement == "CGLOW" and not self.m.cglow_measurement.kernel_supported():
-            glow_levels = self.m.cglow_measurement.levels_kernel_supported()
-            glow_wide = not glow_levels
-            glow_widths = self.m.cglow_measurement.hidden_sizes()
         N = c.N
         shard = shard or ShardInfo(1, 0, B, 0, None)
         if shard.world == 1 and shard.B_global != B:
@@ -660,6 +651,9 @@ class FilterEngine:
             vel_steps = torch.cat([start_state[:, None, 2:4].to(dev), vel_input[:, :T - 1].to(dev)], 1)
             vel_steps = vel_steps.transpose(0, 1).contiguous()  # (T, B, 2)
         dyn, cond, pe, meas = self._blobs(dev)
+        if c.measurement == "CGLOW":  # its kernel (cglow.hip, cglow_levels.hip or cglow_wide.hip), chosen once
+            gk = self.m.cglow_measurement.hip_kernel()
+            glow_meas = lambda enc_t, x_t, out: gk.measurement(pe, meas, enc_t, x_t, out=out, **gk.kwargs)
         lin = ops.linspace_markers(N, dev) if c.resampler == "soft" else None
 
         d = L.FilterDesc()
@@ -877,18 +871,8 @@ class FilterEngine:
                 if wide:
                     ops.measurement(c.measurement, pe, meas, c.n_flows, enc[:, t], hx[:, t], c.meas_prior_std,
                                     out=lik_ext)
-                elif glow_levels:  # L = 2 and / or learn_top (the blob of _blobs is in its layout)
-                    g = self.m.cglow_measurement
-                    ops.cglow_levels_measurement(pe, meas, enc[:, t], hx[:, t], K=g.flow.K, L=g.flow.L,
-                                                 learn_top=g.learn_top, out=lik_ext)
-                elif glow_wide:  # other hidden sizes or bins (the same blob layout at those sizes)
-                    g = self.m.cglow_measurement
-                    ops.cglow_wide_measurement(pe, meas, enc[:, t], hx[:, t], K=g.flow.K, L=g.flow.L,
-                                               learn_top=g.learn_top, widths=glow_widths, y_bins=g.n_bins,
-                                               out=lik_ext)
                 else:
-                    ops.cglow_measurement(pe, meas, enc[:, t], hx[:, t], K=self.m.cglow_measurement.flow.K,
-                                          out=lik_ext)
+                    glow_meas(enc[:, t], hx[:, t], lik_ext)
                 if ev is not None:
                     ev.record_end(dev)
                 d.phase = 2

@@ -436,21 +436,44 @@ def measurement(kind: str, pe_blob, meas_blob, n_flows, enc, x, prior_std=2.5, o
     return lik
 
 
-def cglow_measurement(pe_blob, glow_blob, enc, x, K=1, out=None):
-    """Conditional-GLOW likelihood (model/models.py:280-303) WITHOUT the row-max shift:
-    enc [B, 192] (or rows of a strided [B, T, 192] view), x [B, N, 2] (rows may be strided)
-    -> raw lik [B, N]."""
-    require_device(x, "cglow_measurement")
+def _cglow_meas_args(what, enc, x, out):
+    """The measurement forms' preamble: x [B, N, 2] and enc [B, 192] with the strides the kernels
+    read (rows may be strided), and the [B, N] result (``out`` or new) -> (enc, x, B, N, lik)."""
+    require_device(x, what)
     B, N, _ = x.shape
     if x.stride(2) != 1 or x.stride(1) != 2:
         x = x.contiguous()
     if enc.stride(-1) != 1:
         enc = enc.contiguous()
     if enc.shape[-1] != 192:
-        raise L.NfdpfError("cglow_measurement: frame encodings must be 192 wide (--hiddensize 192)")
+        raise NfdpfError(f"{what}: frame encodings must be 192 wide (--hiddensize 192)")
+    return enc, x, B, N, out if out is not None else torch.empty((B, N), device=x.device, dtype=f32)
+
+
+def _cglow_flow_args(what, x, y, L=1, note=""):
+    """The flow forms' preamble: x, y [M, 3, 8, 8] contiguous, and the outputs z (the final z's
+    shape at L levels) and nll [M] -> (x, y, M, z, nll)."""
+    require_device(x, what)
+    M = x.shape[0]
+    if tuple(x.shape[1:]) != (3, 8, 8) or tuple(y.shape) != tuple(x.shape):
+        raise NfdpfError(f"{what}: x and y must both be [M, 3, 8, 8] ({note}got {tuple(x.shape)}, {tuple(y.shape)})")
+    z = torch.empty((M, 24, 2, 2) if int(L) == 2 else (M, 12, 4, 4), device=x.device, dtype=f32)
+    return _c(x), _c(y), M, z, torch.empty((M,), device=x.device, dtype=f32)
+
+
+def _top_ptr(glow_blob, n, L, learn_top):
+    """Pointer to the [new_mean | new_logs] tail of an n-float levels-layout blob, None without learn_top."""
+    nz = 96 if int(L) == 2 else 192
+    return ptr(glow_blob[n - 2 * nz:]) if learn_top else None
+
+
+def cglow_measurement(pe_blob, glow_blob, enc, x, K=1, out=None):
+    """Conditional-GLOW likelihood (model/models.py:280-303) WITHOUT the row-max shift:
+    enc [B, 192] (or rows of a strided [B, T, 192] view), x [B, N, 2] (rows may be strided)
+    -> raw lik [B, N]."""
+    enc, x, B, N, lik = _cglow_meas_args("cglow_measurement", enc, x, out)
     if int(glow_blob.numel()) != int(lib().nfdpf_cglow_params_size(int(K))):
         raise L.NfdpfError("cglow_measurement: parameter blob does not match flow_depth K")
-    lik = out if out is not None else torch.empty((B, N), device=x.device, dtype=f32)
     check(lib().nfdpf_cglow_measurement(ptr(pe_blob), ptr(glow_blob), int(K), ptr(enc), enc.stride(0), ptr(x),
                                         x.stride(0), B, N, ptr(lik), lik.stride(0), stream_ptr(x.device)),
           "nfdpf_cglow_measurement")
@@ -505,15 +528,9 @@ def cglow_flow_backward(glow_blob, x, y, g_z, g_nll, K=1):
 def cglow_flow(glow_blob, x, y, K=1):
     """CondGlowModel.forward(x, y) (nf/cglow/CGlowModel.py:167-176) -> (z [M,12,4,4], nll [M]);
     x, y [M,3,8,8] (the condition and the flow input, per sample)."""
-    require_device(x, "cglow_flow")
-    M = x.shape[0]
-    if tuple(x.shape[1:]) != (3, 8, 8) or tuple(y.shape) != tuple(x.shape):
-        raise L.NfdpfError(f"cglow_flow: x and y must both be [M, 3, 8, 8] (got {tuple(x.shape)}, {tuple(y.shape)})")
-    x, y = _c(x), _c(y)
+    x, y, M, z, nll = _cglow_flow_args("cglow_flow", x, y)
     if int(glow_blob.numel()) != int(lib().nfdpf_cglow_params_size(int(K))):
         raise L.NfdpfError("cglow_flow: parameter blob does not match flow_depth K")
-    z = torch.empty((M, 12, 4, 4), device=x.device, dtype=f32)
-    nll = torch.empty((M,), device=x.device, dtype=f32)
     check(lib().nfdpf_cglow_flow(ptr(_c(glow_blob)), int(K), ptr(x), ptr(y), int(M), ptr(z), ptr(nll),
                                  stream_ptr(x.device)), "nfdpf_cglow_flow")
     return z, nll
@@ -529,24 +546,15 @@ def _levels_blob(glow_blob, K, L, learn_top, what):
         raise NfdpfError(f"{what}: parameter blob does not match K = {K}, L = {L}, learn_top = {bool(learn_top)} "
                             f"({int(glow_blob.numel())} floats, expected {n})")
     glow_blob = _c(glow_blob)
-    nz = 96 if int(L) == 2 else 192
-    return glow_blob, (ptr(glow_blob[n - 2 * nz:]) if learn_top else None)
+    return glow_blob, _top_ptr(glow_blob, n, L, learn_top)
 
 
 def cglow_levels_measurement(pe_blob, glow_blob, enc, x, K=1, L=1, learn_top=False, out=None):
     """cglow_measurement for num_levels L in 1..2 and / or a learnt top prior
     (nfdpf_cglow_levels_measurement; glow_blob from nfdpf.pack.cglow_levels_tensors): enc [B, 192]
     (rows may be strided), x [B, N, 2] -> raw lik [B, N], no row-max shift."""
-    require_device(x, "cglow_levels_measurement")
-    B, N, _ = x.shape
-    if x.stride(2) != 1 or x.stride(1) != 2:
-        x = x.contiguous()
-    if enc.stride(-1) != 1:
-        enc = enc.contiguous()
-    if enc.shape[-1] != 192:
-        raise NfdpfError("cglow_levels_measurement: frame encodings must be 192 wide (--hiddensize 192)")
+    enc, x, B, N, lik = _cglow_meas_args("cglow_levels_measurement", enc, x, out)
     glow_blob, top = _levels_blob(glow_blob, K, L, learn_top, "cglow_levels_measurement")
-    lik = out if out is not None else torch.empty((B, N), device=x.device, dtype=f32)
     check(lib().nfdpf_cglow_levels_measurement(ptr(pe_blob), ptr(glow_blob), int(K), int(L), top, ptr(enc),
                                                enc.stride(0), ptr(x), x.stride(0), B, N, ptr(lik), lik.stride(0),
                                                stream_ptr(x.device)), "nfdpf_cglow_levels_measurement")
@@ -556,15 +564,8 @@ def cglow_levels_measurement(pe_blob, glow_blob, enc, x, K=1, L=1, learn_top=Fal
 def cglow_levels_flow(glow_blob, x, y, K=1, L=1, learn_top=False):
     """cglow_flow for num_levels L in 1..2 and / or a learnt top prior (nfdpf_cglow_levels_flow):
     x, y [M,3,8,8] -> (the final z, [M,24,2,2] at L = 2 and [M,12,4,4] at L = 1; nll [M])."""
-    require_device(x, "cglow_levels_flow")
-    M = x.shape[0]
-    if tuple(x.shape[1:]) != (3, 8, 8) or tuple(y.shape) != tuple(x.shape):
-        raise NfdpfError(f"cglow_levels_flow: x and y must both be [M, 3, 8, 8] (got {tuple(x.shape)}, "
-                            f"{tuple(y.shape)})")
-    x, y = _c(x), _c(y)
+    x, y, M, z, nll = _cglow_flow_args("cglow_levels_flow", x, y, L)
     glow_blob, top = _levels_blob(glow_blob, K, L, learn_top, "cglow_levels_flow")
-    z = torch.empty((M, 24, 2, 2) if int(L) == 2 else (M, 12, 4, 4), device=x.device, dtype=f32)
-    nll = torch.empty((M,), device=x.device, dtype=f32)
     check(lib().nfdpf_cglow_levels_flow(ptr(glow_blob), int(K), int(L), top, ptr(x), ptr(y), int(M), ptr(z), ptr(nll),
                                         stream_ptr(x.device)), "nfdpf_cglow_levels_flow")
     return z, nll
@@ -590,8 +591,7 @@ def _wide_blob(glow_blob, K, L, learn_top, widths, y_bins, what):
         raise NfdpfError(f"{what}: parameter blob does not match K = {K}, L = {L}, learn_top = {bool(learn_top)}, "
                          f"hidden sizes {xh} / {xs} / {yh} ({int(glow_blob.numel())} floats, expected {n})")
     glow_blob = _c(glow_blob)
-    nz = 96 if int(L) == 2 else 192
-    return glow_blob, (ptr(glow_blob[n - 2 * nz:]) if learn_top else None), (xh, xs, yh), -math.log(y_bins) * 192.0
+    return glow_blob, _top_ptr(glow_blob, n, L, learn_top), (xh, xs, yh), -math.log(y_bins) * 192.0
 
 
 def cglow_wide_measurement(pe_blob, glow_blob, enc, x, K=1, L=1, learn_top=False, widths=(8, 16, 8), y_bins=256.0,
@@ -601,16 +601,8 @@ def cglow_wide_measurement(pe_blob, glow_blob, enc, x, K=1, L=1, learn_top=False
     (nfdpf_cglow_wide_measurement, csrc/cglow_wide.hip; glow_blob from
     nfdpf.pack.cglow_levels_tensors): enc [B, 192] (rows may be strided), x [B, N, 2] -> raw lik
     [B, N], no row-max shift."""
-    require_device(x, "cglow_wide_measurement")
-    B, N, _ = x.shape
-    if x.stride(2) != 1 or x.stride(1) != 2:
-        x = x.contiguous()
-    if enc.stride(-1) != 1:
-        enc = enc.contiguous()
-    if enc.shape[-1] != 192:
-        raise NfdpfError("cglow_wide_measurement: frame encodings must be 192 wide (--hiddensize 192)")
+    enc, x, B, N, lik = _cglow_meas_args("cglow_wide_measurement", enc, x, out)
     glow_blob, top, (xh, xs, yh), ld0 = _wide_blob(glow_blob, K, L, learn_top, widths, y_bins, "cglow_wide_measurement")
-    lik = out if out is not None else torch.empty((B, N), device=x.device, dtype=f32)
     if B * N == 0:  # (empty tensors have no pointer to pass)
         return lik
     check(lib().nfdpf_cglow_wide_measurement(ptr(pe_blob), ptr(glow_blob), int(K), int(L), top, ptr(enc),
@@ -623,15 +615,8 @@ def cglow_wide_flow(glow_blob, x, y, K=1, L=1, learn_top=False, widths=(8, 16, 8
     """cglow_levels_flow at the hidden sizes ``widths`` and any finite y_bins > 0
     (nfdpf_cglow_wide_flow): x, y [M,3,8,8] -> (the final z, [M,24,2,2] at L = 2 and [M,12,4,4]
     at L = 1; nll [M])."""
-    require_device(x, "cglow_wide_flow")
-    M = x.shape[0]
-    if tuple(x.shape[1:]) != (3, 8, 8) or tuple(y.shape) != tuple(x.shape):
-        raise NfdpfError(f"cglow_wide_flow: x and y must both be [M, 3, 8, 8] (192-wide encodings; got "
-                         f"{tuple(x.shape)}, {tuple(y.shape)})")
-    x, y = _c(x), _c(y)
+    x, y, M, z, nll = _cglow_flow_args("cglow_wide_flow", x, y, L, note="192-wide encodings; ")
     glow_blob, top, (xh, xs, yh), ld0 = _wide_blob(glow_blob, K, L, learn_top, widths, y_bins, "cglow_wide_flow")
-    z = torch.empty((M, 24, 2, 2) if int(L) == 2 else (M, 12, 4, 4), device=x.device, dtype=f32)
-    nll = torch.empty((M,), device=x.device, dtype=f32)
     if M == 0:  # (empty tensors have no pointer to pass)
         return z, nll
     check(lib().nfdpf_cglow_wide_flow(ptr(glow_blob), int(K), int(L), top, ptr(x), ptr(y), int(M), ptr(z), ptr(nll),
